@@ -7,7 +7,12 @@ the device from seed = rank (weak scaling: every rank owns its own shard).  One 
 kernels, code transpose).  Codebooks: rank 0 trains them on its first 65,536 rows (GPU
 k-means, 25 iterations, seed 1234) and broadcasts them (RCCL).
 
-Second-level legs (keys of the same JSON line):
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only that: it generates the shard,
+trains the codebooks, warms up, times the K steps, writes the outputs if --dump-outputs is
+given, and prints the JSON line (the keys of the legs below are null).  Everything else runs
+only with --full.
+
+Second-level legs (--full; keys of the same JSON line):
   adc        ADC top-10 of --nq queries (the first rows of rank 0's shard, the reference's
              convention) over all shards (queries broadcast, per-shard LUT
              scan, one RCCL all-gather, on-device merge): queries/s, recall@10 against the
@@ -25,7 +30,14 @@ Second-level legs (keys of the same JSON line):
              registry's `rabitq` route (Extended RaBitQ, 4 bits, 200k x 3072 encode + decode,
              fp64 MFMA roofline of erq_rotate_kernel).
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+  --full: also the CPU baseline and parity legs and every second-level leg above (each can be
+  switched off again with its --no-* option).
+  --dump-outputs DIR: after the timed steps, write what the last timed `mivq_pq_encode` call
+  returned, the PQ codes, as DIR/codes.npy (float32, one row per vector, one column per code
+  byte; DIR/codes_rank<r>.npy per rank when N > 1).  A shard of more than DUMP_ROWS / N rows is
+  sampled: a fixed, seeded, sorted choice of that many rows.  The inputs (rows, codebooks) are
+  seeded, so two runs with the same arguments encode the same data.
   --gpus N > 1 without WORLD_SIZE in the environment starts
   `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process (no
   exec; nothing here touches the GPU before that) and exits with its status; rank 0 prints
@@ -94,6 +106,8 @@ def qscan_valu_roofline(nq, n, M, seconds):
             "valu_instructions_per_search": instr}
 # rigorous relative bound on a canonical fp32 score difference (oracle header): 2 (2 g_96 + u)
 CLEAR_GAP = 3e-5
+DUMP_ROWS = 1 << 18            # --dump-outputs: rows of codes written over all ranks (16 MB of float32 at M = 16)
+DUMP_SEED = 20240229           # seed of the row sample when a shard has more rows than that
 
 
 def log(*a):
@@ -113,6 +127,10 @@ def parse(argv=None):
     ap.add_argument("--gt-queries", type=int, default=100)
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline work")
     ap.add_argument("--data", choices=("gaussian", "clustered"), default="gaussian")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline, parity and second-level legs (off: the headline encode only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the codes of the last timed step as DIR/codes.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-adc", action="store_true")
     ap.add_argument("--no-alt-data", action="store_true")
@@ -279,6 +297,26 @@ def encode_leg(X, C, a, rank, world, dev, steps, warmup, exact=False, legacy=Fal
     bpv = 4 * d + M  # read x, write the codes
     ach = n * bpv / (kern_ms * 1e-3) / 1e9
     return codes, {"wall_s": wall, "kernel_ms": kern_ms, "bytes_per_vector": bpv, "achieved_gbs": ach}
+
+
+def dump_outputs(codes, out_dir, rank, world):
+    """--dump-outputs: the codes buffer as the last timed step left it, as float32 (every byte
+    value is exact), all rows or a fixed seeded sample of them (the same rows in every run with
+    the same --n and --gpus)."""
+    n = codes.shape[0]
+    cap = max(1, DUMP_ROWS // world)
+    if n > cap:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+        sel = codes[torch.from_numpy(rows).to(codes.device)]
+    else:
+        sel = codes
+    arr = sel.cpu().numpy().astype(np.float32)
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    name = "codes" if world == 1 else f"codes_rank{rank}"
+    np.save(d / f"{name}.npy", arr)
+    return {"file": f"{name}.npy", "dtype": "float32", "shape": list(arr.shape), "rows_of_shard": n,
+            "rows": "all" if n <= cap else f"sorted sample of {cap} rows, numpy default_rng({DUMP_SEED}).choice"}
 
 
 def parity_check(X, C, codes, O, max_rows=None, fp64_rows=20000):
@@ -802,6 +840,8 @@ def main():
     if a.dry_run:
         dry_run(a)
         return 0
+    if not a.full:  # a plain run: the headline encode only
+        a.no_cpu_baseline = a.no_adc = a.no_alt_data = a.no_north_star = a.no_config5 = a.no_configs = True
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1:
@@ -823,6 +863,7 @@ def main():
     value = world * a.n / enc["wall_s"]
     log(f"[rank {rank}] encode: {enc['wall_s'] * 1e3:.3f} ms/step wall, {enc['kernel_ms']:.3f} ms/call device")
     workload = f"pq{a.M}_encode_{a.n}x{a.d}"
+    dumped = dump_outputs(codes, a.dump_outputs, rank, world) if a.dump_outputs else None
 
     parity = cpu = None
     if head_only and not a.no_cpu_baseline:
@@ -906,6 +947,7 @@ def main():
             "value": value,
             "unit": "vectors/s",
             "n_gpus": world,
+            "full": a.full,
             "steps": a.steps,
             "warmup": a.warmup,
             "ms_per_step": enc["wall_s"] * 1e3,
@@ -927,6 +969,7 @@ def main():
                                    "pq_resolve_merged_kernel (canonical fp32 re-check of the row-subspaces the filter "
                                    "could not settle) + pq_transpose_codes16_kernel",
                          "bytes_per_vector": enc["bytes_per_vector"], "kernel_ms": enc["kernel_ms"]},
+            "outputs_dumped": dumped,
             "cpu_baseline": cpu,
             "parity_sample": parity,
             "adc": adc,

@@ -131,7 +131,7 @@ def test_bench_two_ranks_one_gpu(dev, tmp_path):
     broadcasts, max-over-ranks timing, the top-k exchange and merge, config #5 -- the code the
     driver's multi-GPU runs execute, with small shapes.  The sharded ADC lists must agree with
     the sharded decode + exact ranking of the same codes (near-ties aside)."""
-    cmd = [sys.executable, "-u", str(ROOT / "bench.py"), "--gpus", "2", "--n", "100000", "--steps", "2",
+    cmd = [sys.executable, "-u", str(ROOT / "bench.py"), "--full", "--gpus", "2", "--n", "100000", "--steps", "2",
            "--warmup", "1", "--nq", "64", "--gt-queries", "32", "--no-cpu-baseline", "--no-alt-data",
            "--no-north-star", "--no-configs", "--config5-rows", "60000", "--config5-nq", "64"]
     p = subprocess.run(cmd, capture_output=True, text=True, env=_env(), timeout=600, cwd=str(tmp_path))

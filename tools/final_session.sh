@@ -16,4 +16,4 @@ bash tools/gpu_session.sh pytest smoke \
   "bash tools/pmc_rq.sh fin" \
   "timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/rqsplit -o run --output-format csv -- python tools/probe_rq.py none --reps 3" \
   "python -u tools/stream_rate.py" \
-  "python -u bench.py"
+  "python -u bench.py --full"

@@ -4,7 +4,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/pmc_adc
 mkdir -p $OUT
-BENCH="python bench.py --no-cpu-baseline --no-alt-data --no-north-star --no-config5 --no-configs --steps 2 --warmup 1"
+BENCH="python bench.py --full --no-cpu-baseline --no-alt-data --no-north-star --no-config5 --no-configs --steps 2 --warmup 1"
 i=0
 for group in "SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE" \
              "SQ_ACTIVE_INST_LDS SQ_INSTS_VALU SQ_WAIT_INST_LDS SQ_BUSY_CYCLES SQ_WAVE_CYCLES"; do

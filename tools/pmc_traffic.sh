@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/pmc_traffic
 mkdir -p $OUT
 KRE="pq_encode_cs_kernel|pq_resolve_merged|pq_transpose_codes|opq_row_scale|opq_split_gemm|sq_encode_f32_vec|rabitq_encode_wide_kernel|erq_rotate_fast_kernel"
-BENCH="python -u bench.py --no-adc --no-cpu-baseline --no-alt-data --no-north-star --no-config5 --steps 3 --warmup 1"
+BENCH="python -u bench.py --full --no-adc --no-cpu-baseline --no-alt-data --no-north-star --no-config5 --steps 3 --warmup 1"
 i=0
 for group in "FETCH_SIZE" "WRITE_SIZE" \
     "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE"; do

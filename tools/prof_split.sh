@@ -7,7 +7,7 @@ tag=$1; shift
 OUT=gpurun_out/prof_$tag
 mkdir -p $OUT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT -o run --output-format csv -- \
-    python bench.py --no-cpu-baseline --no-alt-data --no-north-star --no-config5 --no-configs "$@" > $OUT/bench.log 2>&1
+    python bench.py --full --no-cpu-baseline --no-alt-data --no-north-star --no-config5 --no-configs "$@" > $OUT/bench.log 2>&1
 rc=$?
 echo "rocprofv3 exit $rc"
 [ $rc -ne 0 ] && exit $rc
