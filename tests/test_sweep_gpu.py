@@ -126,10 +126,13 @@ def test_streaming_sweep_local_file(tmp_path):
     assert m["mse"] == pytest.approx(float(((X.astype(np.float64) - rec) ** 2).sum(1).mean()), rel=1e-6)
 
 
-def test_streaming_sweep_grouped_calls_equal_per_batch_calls(tmp_path, monkeypatch):
+@pytest.mark.parametrize("method,margs", [("pq", ["--pq-subquantizers", "8"]), ("opq", ["--opq-quantizers", "8"]),
+                                          ("sq", []), ("rabitq", [])], ids=["pq", "opq", "sq", "rabitq"])
+def test_streaming_sweep_grouped_calls_equal_per_batch_calls(tmp_path, monkeypatch, method, margs):
     """The device encode takes several stream batches per call (streaming_sweep.CALL_ROWS); the
     logged row must equal the one of upstream's one-call-per-batch loop bit for bit (ragged
-    last batch and a group boundary inside the run included)."""
+    last batch and a group boundary inside the run included), for every method the command
+    streams."""
     from typer.testing import CliRunner
 
     from haag_vq.benchmarks import streaming_sweep as ss
@@ -141,7 +144,7 @@ def test_streaming_sweep_grouped_calls_equal_per_batch_calls(tmp_path, monkeypat
     for tag, rows in (("per_batch", 3000), ("grouped", 9000), ("one_call", 1 << 20)):
         monkeypatch.setattr(ss, "CALL_ROWS", rows)
         db = tmp_path / f"{tag}.db"
-        res = CliRunner().invoke(app, ["streaming-sweep", "--method", "pq", "--pq-subquantizers", "8",
+        res = CliRunner().invoke(app, ["streaming-sweep", "--method", method, *margs,
                                        "--training-size", "4096", "--batch-size", "3000",
                                        "--data-path", str(tmp_path / "stream.npy"), "--db-path", str(db)])
         assert res.exit_code == 0, res.output + repr(res.exception)
@@ -162,7 +165,8 @@ def test_sweep_config1_standin_shape(tmp_path, monkeypatch, oracle):
     --pq-bits 8` on a local 100k x 1536 unit-normalised Gaussian file (seed 0).  The logged row
     has the reference's schema and metric set, compression ratio 4 D / M = 768 (row 56), and the
     PQ8 (dsub 192) codes of a 20k-row sample equal the oracle's canonical encode under the
-    codebook the sweep trained."""
+    codebook the sweep trained -- both the codes the sweep itself scored (the output of its
+    compress call, captured during the run) and a fresh encode of the same rows."""
     from typer.testing import CliRunner
 
     import torch
@@ -172,12 +176,21 @@ def test_sweep_config1_standin_shape(tmp_path, monkeypatch, oracle):
     X = np.random.default_rng(0).standard_normal((100_000, 1536), dtype=np.float32)
     X /= np.linalg.norm(X, axis=1, keepdims=True)
     np.save(tmp_path / "dbpedia-100k.npy", X)
-    models = []
+    models, scored = [], []
     build = sw._build_model
 
     def capture(method, config):
-        models.append(build(method, config))
-        return models[-1]
+        model = build(method, config)
+        compress = model.compress
+
+        def recording(rows):  # (rows of the call, its output): the first call is the one the sweep scores
+            out = compress(rows)
+            scored.append((rows.shape[0], out.cpu().numpy() if hasattr(out, "cpu") else np.array(out)))
+            return out
+
+        model.compress = recording
+        models.append(model)
+        return model
 
     monkeypatch.setattr(sw, "_build_model", capture)
     db = tmp_path / "runs.db"
@@ -202,4 +215,8 @@ def test_sweep_config1_standin_shape(tmp_path, monkeypatch, oracle):
     assert C.shape == (8, 256, 192)
     got = pq.compress(torch.from_numpy(X[:20_000]).cuda())
     got = got.cpu().numpy() if hasattr(got, "cpu") else np.asarray(got)
-    np.testing.assert_array_equal(got, oracle.pq_encode(X[:20_000], C))
+    want = oracle.pq_encode(X[:20_000], C)
+    np.testing.assert_array_equal(got, want)
+    rows, codes = scored[0]  # time_compress(model, X): what distortion, pairwise and recall were computed from
+    assert rows == 100_000 and codes.shape == (100_000, 8) and codes.dtype == np.uint8
+    np.testing.assert_array_equal(codes[:20_000], want)
