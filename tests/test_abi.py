@@ -121,6 +121,41 @@ def test_rabitq_search_workspace_bounded():
     assert 0 < nb < rows + 3 * 2 ** 30, nb
 
 
+def test_search_workspace_sizes_pinned():
+    """Every search entry point takes its pointers from the layout its size query reports, so the
+    sizes are part of the ABI callers allocate by.  The numbers were read from the library before
+    each layout moved into one function: filtered ADC shapes (M = 16 / 32, nbits = 8, k <= 32;
+    the last one past the 1 GiB cap of the filtered part lists), fp32-only ADC shapes, the
+    streaming and the tiled flat search, the screened RaBitQ search."""
+    from haag_vq import _native
+
+    lib = _native.load_library()
+    adc = {  # (nq, n, M, nbits, k)
+        (1, 1, 16, 8, 1): 68096,
+        (100, 10_000, 16, 8, 10): 3604992,
+        (1000, 1_000_000, 16, 8, 10): 51332864,
+        (1000, 1_000_000, 32, 8, 32): 154085632,
+        (1000, 1_000_000, 16, 8, 33): 8448000,
+        (17, 5000, 8, 8, 256): 2785280,
+        (17, 5000, 12, 6, 10): 109056,
+        (100_000, 10_000_000, 16, 8, 32): 1763600128,
+    }
+    flat = {  # (nq, n, d, k)
+        (1, 100, 7, 1): 512,
+        (15, 1_000_000, 1536, 10): 2361856,
+        (16, 4096, 1536, 10): 266240,
+        (1000, 1_000_000, 3072, 100): 276544512,
+    }
+    rabitq = {  # (nq, n, d, k)
+        (1000, 1_000_000, 3072, 10): 1121636608,
+        (100_000, 10_000_000, 3072, 10): 4226000128,
+    }
+    for fn, table in ((lib.mivq_adc_search_workspace_bytes, adc), (lib.mivq_flat_search_workspace_bytes, flat),
+                      (lib.mivq_rabitq_search_workspace_bytes, rabitq)):
+        for shape, want in table.items():
+            assert fn(*shape) == want, (fn.__name__, shape, fn(*shape), want)
+
+
 def test_qscan_valu_counts_match_bench():
     """bench.py prices the filtered ADC scan's roofline from the static VALU count of one
     wave-step of adc_qscan_kernel (QSCAN_VALU_PER_STEP); that count must be the built library's."""

@@ -1,4 +1,4 @@
-"""The filtered ADC search (adc.hip: integer-LUT scan + exact fp32 re-rank + certificate, the
+"""The filtered ADC search (adc_filtered.hip: integer-LUT scan + exact fp32 re-rank + certificate, the
 fp32 scan re-run on uncertified queries) returns exactly the canonical top-k of
 FlatQuantizedIndex.search_with_scores' ADC counterpart
 (/root/reference/src/haag_vq/methods/search/flat_quantized_index.py:45-76): the oracle's

@@ -1,5 +1,5 @@
-"""Static VALU count of adc_qscan_kernel's main loop (one wave-step: 64 rows x 16 queries) in the
-built libmivq.so, split by encoding size (32-bit VOP1/VOP2/VOPC vs 64-bit VOP3/VOP3P/literal forms:
+"""Static VALU count of adc_qscan_kernel's main loop (csrc/adc_filtered.hip; one wave-step: 64 rows
+x 16 queries) in the built libmivq.so, split by encoding size (32-bit VOP1/VOP2/VOPC vs 64-bit VOP3/VOP3P/literal forms:
 the VALU-rate probe, tools/probes/valu_rate.hip, measured them at different issue rates).
 
 bench.py's ADC roofline quotes the scan's VALU issue rate from these counts

@@ -365,7 +365,7 @@ int main(int argc, char** argv) {
                     case 4: CM(mivq_pq_encode(D.X, D.n, D.d, D.M, 8, D.C, D.pprep, D.pwork, D.pwb, D.codes, 0, sb)); break;
                     case 5:
                         for (int r = 0; r < 4; ++r)
-                            CM(mivq_adc_search(D.lutp, D.nq, D.codes, D.n, D.M, 8, 10, 0, D.swork, D.swb, D.sd, D.si, sb));
+                            CM(mivq_adc_search(D.lutp, D.nq, D.codes, D.n, D.M, 8, 10, 0, D.swork, D.swb, D.sd, D.si, MIVQ_ADC_AUTO, sb));
                         break;
                     case 6: launch_partner_dma(16, E.Y, (int64_t)E.n * E.d, sink, sb); break;
                     case 7: launch_partner_dma(4, E.Y, (int64_t)E.n * E.d, sink, sb); break;

@@ -147,18 +147,11 @@ constexpr int kRotAP = kRotK + 1;   // A stage row pitch (doubles): [row][k]
 constexpr int kRotBP = kRotT + 1;   // B stage row pitch (doubles): [k][col]
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
-// Tile of workgroup b.  MIVQ_ERQ_XCD (default): the workgroups of one XCD (b % 8, dealt
-// round-robin) take a contiguous range of tiles, so the column tiles of one 128-row block run
-// side by side on one XCD and share its L2 copy of the o strip (3 MB at D = 3072); the round-3
-// order (b itself) spread them over all eight XCDs, each fetching the strip again.
-#ifndef MIVQ_ERQ_XCD
-#define MIVQ_ERQ_XCD 1
-#endif
-#ifndef MIVQ_ERQ_SFIRST  // stage-first loop order in erq_rotate_fast_kernel (61.8 -> 58.6 ms, r04_s25)
-#define MIVQ_ERQ_SFIRST 1
-#endif
+// Tile of workgroup b: the workgroups of one XCD (b % 8, dealt round-robin) take a contiguous
+// range of tiles, so the column tiles of one 128-row block run side by side on one XCD and
+// share its L2 copy of the o strip (3 MB at D = 3072); the round-3 order (b itself) spread
+// them over all eight XCDs, each fetching the strip again.
 __device__ __forceinline__ int64_t erq_tile(int64_t b, int64_t G) {
-    if (!MIVQ_ERQ_XCD) return b;
     const int64_t x = b & 7, j = b >> 3, q = G >> 3, r = G & 7;
     return x * q + (x < r ? x : r) + j;
 }
@@ -331,37 +324,22 @@ __global__ __launch_bounds__(256, 2) void erq_rotate_fast_kernel(const double* _
     gload(0, ra0, rb0);
     gload(kRotK, ra1, rb1);
     sstore(0, ra0, rb0);
-    if (MIVQ_ERQ_SFIRST) {
-        // stage first: each half-trip stores the next slice (loaded a half-trip and more ago)
-        // BEFORE its MFMAs, then issues the loads of the slice three ahead into the freed stage
-        gload(2 * kRotK, ra0, rb0);
-        __syncthreads();
-        for (int ks = 0; ks < nk; ks += 2) {
-            sstore(1, ra1, rb1);                 // slice ks + 1
-            gload((ks + 3) * kRotK, ra1, rb1);
-            slice(0);                            // slice ks
-            __syncthreads();
-            sstore(0, ra0, rb0);                 // slice ks + 2 (past nk: zeros, never read)
-            gload((ks + 4) * kRotK, ra0, rb0);
-            slice(1);                            // slice ks + 1
-            __syncthreads();
-        }
-    } else {
-    __syncthreads();
     // two slices per trip (nk is even: d % 32 == 0) so the register stages stay static and no
-    // branch splits the loop: slice ks computes from LDS stage 0 while slice ks + 2 loads into
-    // the stage slice ks came from; loads past d read zeros, and the last trip's stores of them
-    // into stage 0 are never read
+    // branch splits the loop; loads past d read zeros, and stores of them are never read.
+    // Stage first: each half-trip stores the next slice (loaded a half-trip and more ago)
+    // BEFORE its MFMAs, then issues the loads of the slice three ahead into the freed stage
+    // (load, MFMAs, then store: 61.8 against 58.6 ms, profiles/r04_s25)
+    gload(2 * kRotK, ra0, rb0);
+    __syncthreads();
     for (int ks = 0; ks < nk; ks += 2) {
-        gload((ks + 2) * kRotK, ra0, rb0);
-        slice(0);
-        sstore(1, ra1, rb1);
-        __syncthreads();
+        sstore(1, ra1, rb1);                 // slice ks + 1
         gload((ks + 3) * kRotK, ra1, rb1);
-        slice(1);
-        sstore(0, ra0, rb0);
+        slice(0);                            // slice ks
         __syncthreads();
-    }
+        sstore(0, ra0, rb0);                 // slice ks + 2 (past nk: zeros, never read)
+        gload((ks + 4) * kRotK, ra0, rb0);
+        slice(1);                            // slice ks + 1
+        __syncthreads();
     }
 #pragma unroll
     for (int a = 0; a < 4; ++a)
@@ -431,11 +409,8 @@ extern "C" int mivq_extrabitq_rotate(const double* o, int64_t n, int32_t d, cons
     MIVQ_REQUIRE(o && P && s && o != s, MIVQ_ERR_INVALID, "extrabitq_rotate: null or aliased pointer");
     const int64_t ct = ceil_div(d, kRotT), tiles = ceil_div(n, kRotT) * ct;
     MIVQ_REQUIRE(tiles < ((int64_t)1 << 31), MIVQ_ERR_UNSUPPORTED, "extrabitq_rotate: n=%lld too large", (long long)n);
-#ifndef MIVQ_ERQ_FAST
-#define MIVQ_ERQ_FAST 1
-#endif
     // the fast kernel's buffer offsets are 32-bit: d^2 * 8 bytes of P and 128 rows of o
-    if (MIVQ_ERQ_FAST && d % 32 == 0 && (int64_t)d * d * 8 < ((int64_t)1 << 31)) {
+    if (d % 32 == 0 && (int64_t)d * d * 8 < ((int64_t)1 << 31)) {
         if (transpose)
             hipLaunchKernelGGL(erq_rotate_fast_kernel<1>, dim3((unsigned)tiles), dim3(256), 0, as_stream(stream), o, n, d,
                                P, s, ct);

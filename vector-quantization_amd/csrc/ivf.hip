@@ -178,11 +178,7 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
         if (v != v) v = INFINITY;
         top.offer(valid, v, (uint32_t)j, k, lane, thr_d, thr_i);
     }
-#pragma unroll
-    for (int r = 0; r < RR; ++r) {
-        const int e = r * 64 + lane;
-        if (e < k) { od[row * k + e] = top.d[r]; oi[row * k + e] = top.id[r]; }
-    }
+    top.store(od + row * k, oi + row * k, k, lane);
 }
 
 // ---------------------------------------------------------------- stable bucket sort
@@ -411,151 +407,10 @@ __global__ __launch_bounds__(kIvfWaves * 64) void ivfpq_scan_kernel(
         }
     }
     const int64_t part = (int64_t)blockIdx.x * kIvfWaves + wv;
-    float* od = part_d + (part * nq + q) * k;
-    uint32_t* oi = part_i + (part * nq + q) * k;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int e = r * 64 + lane;
-        if (e < k) { od[e] = top.d[r]; oi[e] = top.id[r]; }
-    }
-}
-
-// Segmented row top-k for the tiled exact search: the (rows, S*L) block is read as rows*S
-// segments of L columns; segment (row, s) writes its k best (value, base + s*L + col) to part
-// part0 + s of the (parts, rows, k) list layout that topk_merge_kernel consumes.
-template <int R>
-__global__ __launch_bounds__(256) void topk_seg_kernel(const float* __restrict__ dist, int64_t rows, int64_t ld,
-                                                       int64_t ncols, int L, int S, int k, int64_t base,
-                                                       int part0, float* __restrict__ part_d,
-                                                       uint32_t* __restrict__ part_i) {
-    const int lane = threadIdx.x & 63;
-    const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (g >= rows * S) return;
-    const int64_t row = g / S;
-    const int s = (int)(g - row * S);
-    const int64_t c0 = (int64_t)s * L;
-    const int64_t c1 = min<int64_t>(ncols, c0 + L);
-    const float* dr = dist + row * ld;
-    WaveTopK<R> top;
-    top.init();
-    float thr_d = INFINITY;
-    uint32_t thr_i = kNoId;
-    // 256 columns per step, four coalesced dword loads per lane, the next step's in flight while
-    // this one is screened; a step none of whose values beats the current k-th element costs one
-    // ballot (round 6: the loop was one dependent 4-B load per 64 columns).  The list is exact
-    // in (dist, id), so the order the candidates are offered in does not change it.
-    float v[4], vn[4];
-    auto ldv = [&](int64_t j0, float (&dst)[4]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int64_t j = j0 + 64 * t + lane;
-            dst[t] = j < c1 ? dr[j] : INFINITY;
-        }
-    };
-    ldv(c0, v);
-    for (int64_t j0 = c0; j0 < c1; j0 += 256) {
-        ldv(j0 + 256, vn);
-        bool any = false;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int64_t j = j0 + 64 * t + lane;
-            if (v[t] != v[t]) v[t] = INFINITY;
-            any = any || (j < c1 && pair_less(v[t], (uint32_t)(base + j), thr_d, thr_i));
-        }
-        if (__ballot(any) != 0ull) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int64_t j = j0 + 64 * t + lane;
-                top.offer(j < c1, v[t], (uint32_t)(base + j), k, lane, thr_d, thr_i);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) v[t] = vn[t];
-    }
-    float* od = part_d + ((int64_t)(part0 + s) * rows + row) * k;
-    uint32_t* oi = part_i + ((int64_t)(part0 + s) * rows + row) * k;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int e = r * 64 + lane;
-        if (e < k) { od[e] = top.d[r]; oi[e] = top.id[r]; }
-    }
-}
-
-// columns per segment (round 6: 16384 measured 3 % faster on the 1000 x 1M estimator search,
-// 1024 30 % slower, profiles/r06_s6; 4096 kept: flat_tiled_cols never goes below one segment,
-// so a longer segment would also raise the distance buffer's floor to nq x kSegL floats)
-constexpr int kSegL = 4096;
-
-int64_t flat_tiled_cols(int64_t nq, int64_t n) {
-    int64_t bc = ((int64_t)1 << 26) / std::max<int64_t>(nq, 1);  // <= 256 MiB of distances per chunk
-    bc = std::max<int64_t>(kSegL, bc / kSegL * kSegL);
-    return std::min<int64_t>(bc, ceil_div(n, kSegL) * kSegL);
-}
-
-template <int R>
-hipError_t launch_topk_seg(const float* dist, int64_t rows, int64_t ld, int64_t ncols, int S, int k, int64_t base,
-                           int part0, float* pd, uint32_t* pi, hipStream_t st) {
-    hipLaunchKernelGGL(topk_seg_kernel<R>, dim3((unsigned)ceil_div(rows * S, 4)), dim3(256), 0, st, dist, rows, ld,
-                       ncols, kSegL, S, k, base, part0, pd, pi);
-    return hipGetLastError();
+    top.store(part_d + (part * nq + q) * k, part_i + (part * nq + q) * k, k, lane);
 }
 
 }  // namespace
-
-int64_t tiled_topk_cols(int64_t nq, int64_t n) { return flat_tiled_cols(nq, n); }
-
-size_t flat_tiled_workspace_bytes(int64_t nq, int64_t n, int k) {
-    const int64_t bc = flat_tiled_cols(nq, n);
-    const int64_t S = bc / kSegL;
-    return align_up((size_t)nq * bc * 4, 256) + 2 * align_up((size_t)(S + 1) * nq * k * 4, 256) +
-           2 * align_up((size_t)nq * k * 4, 256);
-}
-
-// Top-k by tiles: `tile(c0, m, buf)` writes the (nq, m) key block of columns [c0, c0 + m)
-// (row stride m) into buf; a segmented top-k and a running merge (part 0 = the result so
-// far) follow each block.  Keys rank ascending, ties by the smaller id.
-hipError_t launch_tiled_topk(int64_t nq, int64_t n, int k, int64_t id_offset, void* ws, float* dists,
-                             uint32_t* ids, hipStream_t st, const TileFn& tile) {
-    const int64_t bc = flat_tiled_cols(nq, n);
-    const int S = (int)(bc / kSegL);
-    unsigned char* p = static_cast<unsigned char*>(ws);
-    float* buf = reinterpret_cast<float*>(p);
-    p += align_up((size_t)nq * bc * 4, 256);
-    float* pd = reinterpret_cast<float*>(p);
-    p += align_up((size_t)(S + 1) * nq * k * 4, 256);
-    uint32_t* pi = reinterpret_cast<uint32_t*>(p);
-    p += align_up((size_t)(S + 1) * nq * k * 4, 256);
-    float* rd = reinterpret_cast<float*>(p);
-    p += align_up((size_t)nq * k * 4, 256);
-    uint32_t* ri = reinterpret_cast<uint32_t*>(p);
-    hipError_t e = hipSuccess;
-    int nparts = 0;  // parts holding data in pd/pi (part 0 = running result once set)
-    for (int64_t c0 = 0; c0 < n; c0 += bc) {
-        const int64_t m = std::min<int64_t>(bc, n - c0);
-        e = tile(c0, m, buf);
-        if (e != hipSuccess) return e;
-        const int Sc = (int)ceil_div(m, kSegL);
-        const int part0 = nparts == 0 ? 0 : 1;
-        switch ((k + 63) / 64) {
-            case 1: e = launch_topk_seg<1>(buf, nq, m, m, Sc, k, id_offset + c0, part0, pd, pi, st); break;
-            case 2: e = launch_topk_seg<2>(buf, nq, m, m, Sc, k, id_offset + c0, part0, pd, pi, st); break;
-            case 3: e = launch_topk_seg<3>(buf, nq, m, m, Sc, k, id_offset + c0, part0, pd, pi, st); break;
-            default: e = launch_topk_seg<4>(buf, nq, m, m, Sc, k, id_offset + c0, part0, pd, pi, st); break;
-        }
-        if (e != hipSuccess) return e;
-        nparts = part0 + Sc;
-        const bool last = c0 + bc >= n;
-        e = launch_topk_merge(pd, pi, nparts, nq, k, last ? dists : rd, last ? ids : ri, st);
-        if (e != hipSuccess) return e;
-        if (!last) {  // the merged list becomes part 0
-            e = hipMemcpyAsync(pd, rd, (size_t)nq * k * 4, hipMemcpyDeviceToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(pi, ri, (size_t)nq * k * 4, hipMemcpyDeviceToDevice, st);
-            if (e != hipSuccess) return e;
-            nparts = 1;
-        }
-    }
-    return e;
-}
 
 // Exact top-k by tiles: pairwise chains for a column chunk, then launch_tiled_topk's
 // segmented top-k and running merge.  Same chains and (dist, id) order as flat_scan.
@@ -649,13 +504,12 @@ extern "C" int mivq_topk_rows(const float* dist, int64_t n, int64_t m, int32_t k
     MIVQ_REQUIRE((dist || m == 0) && out_d && out_i, MIVQ_ERR_INVALID, "topk_rows: null pointer");
     const dim3 grid((unsigned)ceil_div(n, 4)), block(256);
     hipStream_t st = as_stream(stream);
-    switch (k == 1 ? 0 : (k + 63) / 64) {
-        case 0: hipLaunchKernelGGL(topk_rows_kernel<0>, grid, block, 0, st, dist, n, m, k, out_d, out_i); break;
-        case 1: hipLaunchKernelGGL(topk_rows_kernel<1>, grid, block, 0, st, dist, n, m, k, out_d, out_i); break;
-        case 2: hipLaunchKernelGGL(topk_rows_kernel<2>, grid, block, 0, st, dist, n, m, k, out_d, out_i); break;
-        case 3: hipLaunchKernelGGL(topk_rows_kernel<3>, grid, block, 0, st, dist, n, m, k, out_d, out_i); break;
-        default: hipLaunchKernelGGL(topk_rows_kernel<4>, grid, block, 0, st, dist, n, m, k, out_d, out_i); break;
-    }
+    if (k == 1)
+        hipLaunchKernelGGL(topk_rows_kernel<0>, grid, block, 0, st, dist, n, m, k, out_d, out_i);
+    else
+        with_topk_regs(k, [&](auto R) {
+            hipLaunchKernelGGL(topk_rows_kernel<decltype(R)::value>, grid, block, 0, st, dist, n, m, k, out_d, out_i);
+        });
     return check_launch("topk_rows");
 }
 
@@ -764,13 +618,10 @@ extern "C" int mivq_ivfpq_search(const float* lut, int64_t nq, int32_t M, int32_
     float* pd = static_cast<float*>(workspace);
     uint32_t* pi = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(workspace) +
                                                align_up((size_t)parts * nq * k * sizeof(float), 256));
-    hipError_t e;
-    switch ((k + 63) / 64) {
-        case 1: e = launch_ivf_scan_m<1>(l2, lut, nq, M, ksub, probe_d, probe_l, nprobe, offsets, list_codes, list_ids, tau, k, pd, pi, st); break;
-        case 2: e = launch_ivf_scan_m<2>(l2, lut, nq, M, ksub, probe_d, probe_l, nprobe, offsets, list_codes, list_ids, tau, k, pd, pi, st); break;
-        case 3: e = launch_ivf_scan_m<3>(l2, lut, nq, M, ksub, probe_d, probe_l, nprobe, offsets, list_codes, list_ids, tau, k, pd, pi, st); break;
-        default: e = launch_ivf_scan_m<4>(l2, lut, nq, M, ksub, probe_d, probe_l, nprobe, offsets, list_codes, list_ids, tau, k, pd, pi, st); break;
-    }
+    hipError_t e = with_topk_regs(k, [&](auto R) {
+        return launch_ivf_scan_m<decltype(R)::value>(l2, lut, nq, M, ksub, probe_d, probe_l, nprobe, offsets, list_codes,
+                                                     list_ids, tau, k, pd, pi, st);
+    });
     if (e != hipSuccess) return set_error(MIVQ_ERR_HIP, "ivfpq_scan: %s", hipGetErrorString(e));
     e = launch_topk_merge(pd, pi, parts, nq, k, dists, ids, st);
     if (e != hipSuccess) return set_error(MIVQ_ERR_HIP, "ivfpq merge: %s", hipGetErrorString(e));

@@ -17,12 +17,6 @@
 namespace mivq {
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(256) void rabitq_encode_kernel(const float* __restrict__ x, int64_t n, int d,
                                                             const float* __restrict__ centroid, int metric,
@@ -182,11 +176,8 @@ extern "C" int mivq_rabitq_encode(const float* x, int64_t n, int32_t d, const fl
     if (n == 0) return MIVQ_OK;
     MIVQ_REQUIRE(x && codes, MIVQ_ERR_INVALID, "rabitq_encode: null pointer");
     const bool vec = (d % 4 == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0);
-#ifndef MIVQ_RQ_WIDE
-#define MIVQ_RQ_WIDE 1
-#endif
     const int ni = d / 512;
-    const bool wide = MIVQ_RQ_WIDE && vec && d % 512 == 0 && reinterpret_cast<uintptr_t>(centroid) % 16 == 0;
+    const bool wide = vec && d % 512 == 0 && reinterpret_cast<uintptr_t>(centroid) % 16 == 0;
     const dim3 grid((unsigned)ceil_div(n, 4));
     if (wide && ni % 6 == 0)
         hipLaunchKernelGGL(rabitq_encode_wide_kernel<6>, grid, dim3(256), 0, as_stream(stream), x, n, d, centroid,

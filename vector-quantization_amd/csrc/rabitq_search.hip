@@ -581,11 +581,7 @@ __global__ __launch_bounds__(256) void rq_screen_merge_kernel(float* __restrict_
         const uint32_t iv = valid ? cix[j] : kNoId;
         top.offer(valid, dv, iv, k, lane, thr_d, thr_i);
     }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int e = r * 64 + lane;
-        if (e < k) { run_d[q * k + e] = top.d[r]; run_i[q * k + e] = top.id[r]; }
-    }
+    top.store(run_d + q * k, run_i + q * k, k, lane);
     if (lane == 0) cnt[q] = 0;
 }
 
@@ -706,11 +702,8 @@ extern "C" int mivq_rabitq_search(const uint8_t* codes, int64_t n, int32_t d, co
     }
     const bool mfma = qb > 0 && (d % 32) == 0 && (reinterpret_cast<uintptr_t>(codes) % 4) == 0;
     // the multi-query kernel for d % 512 == 0 (32, 64 or 128 queries per workgroup by nq)
-#ifndef MIVQ_RQ_MQ
-#define MIVQ_RQ_MQ 1
-#endif
     const int nqb_mq = nq > 64 ? 4 : nq > 32 ? 2 : 1;
-    const bool mq = MIVQ_RQ_MQ && mfma && (d % kEstKC) == 0;
+    const bool mq = mfma && (d % kEstKC) == 0;
     // multi-query kernel: two staging stages, the per-query and per-wave epilogue terms
     const size_t smem = mq ? (size_t)2 * 32 * nqb_mq * kEstQP + 32 * nqb_mq * 32 + kEstWaves * 512
                            : (size_t)32 * (d + 16);
@@ -776,13 +769,11 @@ extern "C" int mivq_rabitq_search(const uint8_t* codes, int64_t n, int32_t d, co
             e = launch_mq(mq_screen, c0, m, nullptr, scr);
             if (e != hipSuccess) break;
             const dim3 grid((unsigned)ceil_div(nq, 4)), block(256);
-            switch ((k + 63) / 64) {
-                case 1: hipLaunchKernelGGL(rq_screen_merge_kernel<1>, grid, block, 0, st, dists, ids, nq, k, cnt, scr.cand_d, scr.cand_i, cap); break;
-                case 2: hipLaunchKernelGGL(rq_screen_merge_kernel<2>, grid, block, 0, st, dists, ids, nq, k, cnt, scr.cand_d, scr.cand_i, cap); break;
-                case 3: hipLaunchKernelGGL(rq_screen_merge_kernel<3>, grid, block, 0, st, dists, ids, nq, k, cnt, scr.cand_d, scr.cand_i, cap); break;
-                default: hipLaunchKernelGGL(rq_screen_merge_kernel<4>, grid, block, 0, st, dists, ids, nq, k, cnt, scr.cand_d, scr.cand_i, cap); break;
-            }
-            e = hipGetLastError();
+            e = with_topk_regs(k, [&](auto R) {
+                hipLaunchKernelGGL(rq_screen_merge_kernel<decltype(R)::value>, grid, block, 0, st, dists, ids, nq, k, cnt,
+                                   scr.cand_d, scr.cand_i, cap);
+                return hipGetLastError();
+            });
         }
     }
     if (e != hipSuccess) return set_error(MIVQ_ERR_HIP, "rabitq_search: %s", hipGetErrorString(e));

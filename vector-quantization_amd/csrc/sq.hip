@@ -132,10 +132,8 @@ __global__ __launch_bounds__(256) void sq_encode_f32_vec_kernel(const float* __r
     for (int64_t rbk = blockIdx.y; rbk * kSqRows < n; rbk += gridDim.y) {
     const int64_t r0 = rbk * kSqRows + (threadIdx.x >> 6);
     const int64_t r1 = min(n, (rbk + 1) * kSqRows);
-#ifndef MIVQ_SQ_DEPTH  // rows per wave whose loads are in flight together
-#define MIVQ_SQ_DEPTH 4  // 8: 3.75 vs 2.98 ms per 1M x 3072 (profiles/r04_s15)
-#endif
-    constexpr int SQD = MIVQ_SQ_DEPTH;
+    // rows per wave whose loads are in flight together (8: 3.75 vs 2.98 ms per 1M x 3072, profiles/r04_s15)
+    constexpr int SQD = 4;
     for (int64_t i0 = r0; i0 < r1; i0 += 4 * SQD) {
         float4 xa[SQD], xb[SQD];
 #pragma unroll

@@ -1,4 +1,5 @@
-// topk.h — the wave-resident exact top-k shared by the search kernels (adc.hip, ivf.hip).
+// topk.h — the wave-resident exact top-k shared by the search kernels, and the launchers of
+// topk.hip (list merge, tiled top-k).
 // Elements are (dist, id) pairs ranked ascending by dist, then id; NaN is mapped to +inf by
 // the callers, the sentinel is (+inf, kNoId).
 #pragma once
@@ -6,6 +7,7 @@
 #include "mivq_common.h"
 
 #include <functional>
+#include <type_traits>
 
 namespace mivq {
 
@@ -77,14 +79,34 @@ struct WaveTopK {
             kth(k, thr_d, thr_i);
         }
     }
+    // elements 0 .. k-1 to od[0 .. k), oi[0 .. k)
+    __device__ __forceinline__ void store(float* od, uint32_t* oi, int k, int lane) const {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int e = r * 64 + lane;
+            if (e < k) { od[e] = d[r]; oi[e] = id[r]; }
+        }
+    }
 };
 
+// Host side: f(std::integral_constant<int, R>) for the list registers R = ceil(k / 64) of a
+// k <= 256 search, so the caller names its kernel template once.
+template <typename F>
+auto with_topk_regs(int k, F&& f) {
+    switch ((k + 63) / 64) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        default: return f(std::integral_constant<int, 4>{});
+    }
+}
+
 // Merges per-part sorted lists laid out (parts, nq, k) into (nq, k); parts == 0 writes the
-// sentinel everywhere.  Defined in adc.hip.
+// sentinel everywhere.  (topk.hip)
 hipError_t launch_topk_merge(const float* pd, const uint32_t* pi, int parts, int64_t nq, int k, float* od,
                              uint32_t* oi, hipStream_t st, const int* qlist = nullptr, const int* qcount = nullptr);
 
-// Tiled top-k (ivf.hip): a key-block producer + segmented top-k + running merge.  The
+// Tiled top-k (topk.hip): a key-block producer + segmented top-k + running merge.  The
 // workspace of flat_tiled_workspace_bytes serves both launchers.
 using TileFn = std::function<hipError_t(int64_t c0, int64_t m, float* buf)>;
 hipError_t launch_tiled_topk(int64_t nq, int64_t n, int k, int64_t id_offset, void* ws, float* dists,
@@ -92,7 +114,8 @@ hipError_t launch_tiled_topk(int64_t nq, int64_t n, int k, int64_t id_offset, vo
 // Columns per key block of launch_tiled_topk (a multiple of its 4096-column segment; the key
 // block is nq x that many floats at the start of its workspace).
 int64_t tiled_topk_cols(int64_t nq, int64_t n);
-// Tiled exact brute force (ivf.hip): pairwise chains + segmented top-k + running merge.
+// Workspace of the tiled exact brute force (topk.hip), and its launcher (ivf.hip, beside the
+// pairwise kernel k-means shares): pairwise chains + segmented top-k + running merge.
 size_t flat_tiled_workspace_bytes(int64_t nq, int64_t n, int k);
 hipError_t launch_flat_tiled(const float* q, int64_t nq, const float* x, int64_t n, int d, int metric, int k,
                              int64_t id_offset, void* ws, float* dists, uint32_t* ids, hipStream_t st);
