@@ -211,14 +211,36 @@ size_t mivq_adc_search_workspace_bytes(int64_t nq, int64_t n, int32_t M, int32_t
 int mivq_adc_search(const float* lut, int64_t nq, const uint8_t* codes, int64_t n, int32_t M,
                     int32_t nbits, int32_t k, int64_t id_offset, void* workspace,
                     size_t workspace_bytes, float* dists, uint32_t* ids, uint32_t flags, void* stream);
-/* Exact brute-force top-k over an f32 database (the decode-then-search path of
- * FlatQuantizedIndex for SQ / RaBitQ reconstructions, flat_quantized_index.py:57-76):
+/* Exact brute-force top-k over an f32 database (ground truth; the decode-then-search path of
+ * FlatQuantizedIndex, flat_quantized_index.py:57-76, for the quantizers without a code-domain
+ * search below: f64-fitted SQ, Extended RaBitQ):
  *   L2: dist = fmaf chain over t of (q_t - x_t)^2;  IP: dist = -(fmaf chain of q_t * x_t)
  * ranked ascending by (dist, id) exactly like mivq_adc_search (callers negate IP back). */
 size_t mivq_flat_search_workspace_bytes(int64_t nq, int64_t n, int32_t d, int32_t k);
 int mivq_flat_search(const float* q, int64_t nq, const float* x, int64_t n, int32_t d,
                      int32_t metric, int32_t k, int64_t id_offset, void* workspace,
                      size_t workspace_bytes, float* dists, uint32_t* ids, void* stream);
+/* The same exact search over SQ / RaBitQ-1 codes, without the fp32 database: the codes are
+ * read once and dequantised in registers to the floats mivq_sq_decode_f32 / mivq_rabitq_decode
+ * write, so dists and ids are bit-identical to decode + mivq_flat_search (same chains, same
+ * (dist, id) order, NaN ranks as +inf, missing slots (+inf, 0xFFFFFFFF)).  The workspace holds
+ * part lists / key blocks only, never decoded rows.
+ *   SQ:     codes, lo, den, nbits as in mivq_sq_decode_f32 (16-bit codes 2-byte aligned);
+ *           x^_t = (level / (2^nbits - 1)) * den_t + lo_t, one rounding per step.
+ *   RaBitQ: codes (n, ceil(d/8) + 8) rows of mivq_rabitq_encode, centroid may be NULL;
+ *           x^_t = +-(0.5 * mult * 2 * (1/sqrt(d))) + c_t (not the estimator of
+ *           mivq_rabitq_search: the exact distance to the decoded row).
+ * Rows need no alignment; 16-byte aligned rows are read with 16-byte loads. */
+size_t mivq_sq_flat_search_workspace_bytes(int64_t nq, int64_t n, int32_t d, int32_t k);
+int mivq_sq_flat_search(const float* q, int64_t nq, const void* codes, int64_t n, int32_t d,
+                        const float* lo, const float* den, int32_t nbits, int32_t metric, int32_t k,
+                        int64_t id_offset, void* workspace, size_t workspace_bytes, float* dists,
+                        uint32_t* ids, void* stream);
+size_t mivq_rabitq_flat_search_workspace_bytes(int64_t nq, int64_t n, int32_t d, int32_t k);
+int mivq_rabitq_flat_search(const float* q, int64_t nq, const uint8_t* codes, int64_t n, int32_t d,
+                            const float* centroid, int32_t metric, int32_t k, int64_t id_offset,
+                            void* workspace, size_t workspace_bytes, float* dists, uint32_t* ids,
+                            void* stream);
 /* Merges `parts` sorted (nq, k) lists laid out (parts, nq, k) into one sorted (nq, k) list
  * with the same (dist, id) order — the on-device merge after the RCCL all-gather. */
 int mivq_topk_merge(const float* dists_in, const uint32_t* ids_in, int32_t parts, int64_t nq,

@@ -1,0 +1,557 @@
+// code_search.hip — exact flat search over SQ-4/8/16 and RaBitQ-1 codes on gfx950.
+//
+// The code-domain siblings of flat_search.hip's two paths: the packed codes are read once and
+// dequantised in registers, so no fp32 copy of the database exists at any point.  Every
+// reconstruction x^_t is the float the decode kernels write (sq.hip sq_decode_kernel,
+// rabitq.hip rabitq_decode_kernel; one rounding per step, -ffp-contract=off) and the distances
+// are the chains of mivq_flat_search, so ids and distances are bit-identical to
+// decode + mivq_flat_search.
+//
+//   code_scan_kernel      the flat_scan_kernel shape: QB queries and the per-dimension
+//                         parameters (SQ: den, lo; RaBitQ: centroid) in LDS, lane = database
+//                         row, WaveTopK lists merged by launch_topk_merge.  A row is read with
+//                         16-B (RaBitQ: 8-B) loads while whole loads fit and the rows are that
+//                         aligned, then 4-B loads, then single code elements (the tail, and
+//                         every row of an unaligned database).
+//   code_pairwise_kernel  the pairwise_kernel shape (128 x 64 tile, k-slices of 16 in LDS) as
+//                         launch_tiled_topk's TileFn: the database side of a slice is fetched
+//                         as codes and dequantised before it is stashed.
+//
+// The choice between the two is flat_use_tiled(nq, n); both produce the same chains.
+#include "adc_internal.h"
+#include "topk.h"
+
+namespace mivq {
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+enum : int { kSq4 = 0, kSq8 = 1, kSq16 = 2, kRbq = 3 };
+
+// ---------------------------------------------------------------- code formats
+template <int FMT>
+struct Fmt {
+    // dims per 32-bit word of codes
+    static constexpr int kWordDims = FMT == kSq4 ? 8 : FMT == kSq8 ? 4 : FMT == kSq16 ? 2 : 32;
+    // words per wide load of the scan (16 B; 8 B for RaBitQ, whose rows of d % 64 == 0 are 8-B aligned)
+    static constexpr int kWideWords = FMT == kRbq ? 2 : 4;
+    // per-dimension parameter arrays: SQ {den, lo}, RaBitQ {centroid}
+    static constexpr int kParams = FMT == kRbq ? 1 : 2;
+    static constexpr float kLevels = FMT == kSq4 ? 15.0f : FMT == kSq8 ? 255.0f : 65535.0f;
+    static constexpr float kRcpLevels = 1.0f / kLevels;  // RN(1 / L)
+
+    __host__ __device__ static int code_bytes(int d) {
+        return FMT == kSq4 ? (d + 1) / 2 : FMT == kSq8 ? d : FMT == kSq16 ? 2 * d : (d + 7) / 8;
+    }
+    __host__ __device__ static int row_bytes(int d) { return code_bytes(d) + (FMT == kRbq ? 8 : 0); }
+    // byte offset of dimension t (a multiple of kWordDims) in a row
+    __device__ static int byte_of(int t) { return FMT == kSq4 ? t >> 1 : FMT == kSq8 ? t : FMT == kSq16 ? 2 * t : t >> 3; }
+
+    // level (SQ) / sign bit (RaBitQ) of dimension u of the little-endian words w[]
+    template <int NW>
+    __device__ __forceinline__ static uint32_t level(const uint32_t (&w)[NW], int u) {
+        if (FMT == kSq8) return (w[u >> 2] >> (8 * (u & 3))) & 0xFFu;
+        if (FMT == kSq16) return (w[u >> 1] >> (16 * (u & 1))) & 0xFFFFu;
+        if (FMT == kSq4) {  // even dimension in the high nibble
+            const uint32_t b = (w[u >> 3] >> (8 * ((u >> 1) & 3))) & 0xFFu;
+            return (u & 1) ? (b & 0x0Fu) : (b >> 4);
+        }
+        return (w[u >> 5] >> (u & 31)) & 1u;
+    }
+    // the same for dimension t of row `cr`, one code element at a time
+    __device__ __forceinline__ static uint32_t level_at(const uint8_t* cr, int t) {
+        if (FMT == kSq8) return cr[t];
+        if (FMT == kSq16) return reinterpret_cast<const uint16_t*>(cr)[t];
+        if (FMT == kSq4) {
+            const uint32_t b = cr[t >> 1];
+            return (t & 1) ? (b & 0x0Fu) : (b >> 4);
+        }
+        return (cr[t >> 3] >> (t & 7)) & 1u;
+    }
+    // x^_t.  SQ: a = den_t, b = lo_t, fadd(fmul(fdiv(level, L), den_t), lo_t) with the division as
+    // the reciprocal sequence of sq.hip's div_rn_rcp (RN(level / L) for every level 0 .. L).
+    // RaBitQ: a = c_t (0 without a centroid), p the row's fmul(fmul(fmul(0.5, mult), 2), 1/sqrt(d)).
+    __device__ __forceinline__ static float dequant(uint32_t lv, float a, float b, float p) {
+        if (FMT == kRbq) return __fadd_rn(lv ? p : -p, a);
+        const float f = (float)lv;
+        const float q0 = __fmul_rn(f, kRcpLevels);
+        const float e = __builtin_fmaf(-q0, kLevels, f);
+        const float s = __builtin_fmaf(e, kRcpLevels, q0);
+        return __fadd_rn(__fmul_rn(s, a), b);
+    }
+    // RaBitQ: p of the row (mult is the second trailer float, read byte-wise: rows are unaligned)
+    __device__ __forceinline__ static float row_scale(const uint8_t* cr, int d) {
+        if (FMT != kRbq) return 0.0f;
+        const int nb = (d + 7) / 8;
+        uint32_t mu = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) mu |= (uint32_t)cr[nb + 4 + q] << (8 * q);
+        const float inv_d_sqrt = __fdiv_rn(1.0f, sqrtf((float)d));
+        return __fmul_rn(__fmul_rn(__fmul_rn(0.5f, __uint_as_float(mu)), 2.0f), inv_d_sqrt);
+    }
+};
+
+// ---------------------------------------------------------------- streaming scan
+// NW loaded words = NW * kWordDims (a multiple of 4) dimensions from t0 (a multiple of 4) on:
+// four at a time, the parameters and the queries as 16-B LDS reads.
+template <int FMT, int NW, int QB>
+__device__ __forceinline__ void scan_words(const uint32_t (&w)[NW], int t0, const float* qv, int dp, const float* pa,
+                                           const float* pb, float p, bool l2, float (&dist)[QB]) {
+    constexpr int ND = NW * Fmt<FMT>::kWordDims;
+    static_assert(ND % 4 == 0, "whole groups of four dimensions");
+#pragma unroll
+    for (int g = 0; g < ND; g += 4) {
+        const float4 a4 = *reinterpret_cast<const float4*>(pa + t0 + g);
+        float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (FMT != kRbq) b4 = *reinterpret_cast<const float4*>(pb + t0 + g);
+        const float x0 = Fmt<FMT>::dequant(Fmt<FMT>::level(w, g + 0), a4.x, b4.x, p);
+        const float x1 = Fmt<FMT>::dequant(Fmt<FMT>::level(w, g + 1), a4.y, b4.y, p);
+        const float x2 = Fmt<FMT>::dequant(Fmt<FMT>::level(w, g + 2), a4.z, b4.z, p);
+        const float x3 = Fmt<FMT>::dequant(Fmt<FMT>::level(w, g + 3), a4.w, b4.w, p);
+#pragma unroll
+        for (int qq = 0; qq < QB; ++qq) {
+            const float4 qf = *reinterpret_cast<const float4*>(qv + qq * dp + t0 + g);
+            if (l2) {
+                float df = __fsub_rn(qf.x, x0); dist[qq] = __builtin_fmaf(df, df, dist[qq]);
+                df = __fsub_rn(qf.y, x1); dist[qq] = __builtin_fmaf(df, df, dist[qq]);
+                df = __fsub_rn(qf.z, x2); dist[qq] = __builtin_fmaf(df, df, dist[qq]);
+                df = __fsub_rn(qf.w, x3); dist[qq] = __builtin_fmaf(df, df, dist[qq]);
+            } else {
+                dist[qq] = __builtin_fmaf(qf.x, x0, dist[qq]);
+                dist[qq] = __builtin_fmaf(qf.y, x1, dist[qq]);
+                dist[qq] = __builtin_fmaf(qf.z, x2, dist[qq]);
+                dist[qq] = __builtin_fmaf(qf.w, x3, dist[qq]);
+            }
+        }
+    }
+}
+
+// grid (nchunks, ceil(nq / QB)), block 1024.  LDS: [QB][dp] queries, then kParams x [dp]
+// parameters, dp = d rounded up to 4 (16-B aligned rows; the padding is never read).
+// `wide` / `narrow`: every row start is aligned for the wide (16 / 8 B) / the 4-B loads.
+template <int FMT, int R, int QB>
+__global__ __launch_bounds__(kScanWaves * 64) void code_scan_kernel(
+    const float* __restrict__ q, int64_t nq, const uint8_t* __restrict__ codes, int64_t n, int d,
+    const float* __restrict__ ga, const float* __restrict__ gb, int metric, int k, int64_t id_offset, int64_t chunk_rows,
+    int wide, int narrow, float* __restrict__ part_d, uint32_t* __restrict__ part_i) {
+    using F = Fmt<FMT>;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int dp = (d + 3) & ~3;
+    float* qv = smem;             // [QB][dp]
+    float* pa = smem + QB * dp;   // SQ den / RaBitQ centroid
+    float* pb = pa + dp;          // SQ lo
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t q0 = (int64_t)blockIdx.y * QB;
+    const int nqb = (int)min<int64_t>(QB, nq - q0);
+    for (int qq = 0; qq < nqb; ++qq)
+        for (int t = tid; t < d; t += kScanWaves * 64) qv[qq * dp + t] = q[(q0 + qq) * d + t];
+    for (int t = tid; t < d; t += kScanWaves * 64) {
+        pa[t] = ga ? ga[t] : 0.0f;
+        if (FMT != kRbq) pb[t] = gb[t];
+    }
+    __syncthreads();
+    WaveTopK<R> top[QB];
+    float thr_d[QB];
+    uint32_t thr_i[QB];
+#pragma unroll
+    for (int qq = 0; qq < QB; ++qq) {
+        top[qq].init();
+        thr_d[qq] = INFINITY;
+        thr_i[qq] = kNoId;
+    }
+    const bool l2 = metric == MIVQ_METRIC_L2;
+    const int64_t rbeg = (int64_t)blockIdx.x * chunk_rows;
+    const int64_t rend = min(n, rbeg + chunk_rows);
+    const int64_t stride = F::row_bytes(d);
+    constexpr int NDW = F::kWideWords * F::kWordDims;
+    const int twide = wide ? d / NDW * NDW : 0;  // dimensions covered by whole wide loads
+    for (int64_t base = rbeg + (int64_t)wv * 64; base < rend; base += kScanWaves * 64) {
+        const int64_t row = base + lane;
+        const bool valid = row < rend;
+        float dist[QB];
+#pragma unroll
+        for (int qq = 0; qq < QB; ++qq) dist[qq] = 0.0f;
+        if (valid) {
+            const uint8_t* cr = codes + row * stride;
+            const float p = F::row_scale(cr, d);
+            int t = 0;
+            for (; t < twide; t += NDW) {
+                uint32_t w[F::kWideWords];
+                if constexpr (F::kWideWords == 4) {
+                    const uint4 v = *reinterpret_cast<const uint4*>(cr + F::byte_of(t));
+                    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+                } else {
+                    const uint2 v = *reinterpret_cast<const uint2*>(cr + F::byte_of(t));
+                    w[0] = v.x; w[1] = v.y;
+                }
+                scan_words<FMT, F::kWideWords, QB>(w, t, qv, dp, pa, pb, p, l2, dist);
+            }
+            if constexpr (F::kWordDims % 4 == 0) {  // (an SQ-16 word is half a group: no 4-B step)
+                if (narrow) {
+                    for (; t + F::kWordDims <= d; t += F::kWordDims) {
+                        const uint32_t w[1] = {*reinterpret_cast<const uint32_t*>(cr + F::byte_of(t))};
+                        scan_words<FMT, 1, QB>(w, t, qv, dp, pa, pb, p, l2, dist);
+                    }
+                }
+            }
+            for (; t < d; ++t) {
+                const float xh = F::dequant(F::level_at(cr, t), pa[t], FMT != kRbq ? pb[t] : 0.0f, p);
+#pragma unroll
+                for (int qq = 0; qq < QB; ++qq) {
+                    if (l2) {
+                        const float df = __fsub_rn(qv[qq * dp + t], xh);
+                        dist[qq] = __builtin_fmaf(df, df, dist[qq]);
+                    } else {
+                        dist[qq] = __builtin_fmaf(qv[qq * dp + t], xh, dist[qq]);
+                    }
+                }
+            }
+        }
+        const uint32_t gid = (uint32_t)(id_offset + row);
+#pragma unroll
+        for (int qq = 0; qq < QB; ++qq) {
+            if (qq >= nqb) break;
+            float dv = l2 ? dist[qq] : -dist[qq];
+            if (dv != dv) dv = INFINITY;
+            top[qq].offer(valid, dv, gid, k, lane, thr_d[qq], thr_i[qq]);
+        }
+    }
+    const int64_t part = (int64_t)blockIdx.x * kScanWaves + wv;
+#pragma unroll
+    for (int qq = 0; qq < QB; ++qq) {
+        if (qq < nqb) top[qq].store(part_d + (part * nq + q0 + qq) * k, part_i + (part * nq + q0 + qq) * k, k, lane);
+    }
+}
+
+// Queries per scan workgroup: the queries and the `params` parameter rows share the LDS.
+int code_qb(int d, int params) {
+    const int64_t per = (int64_t)((d + 3) & ~3) * 4;
+    if (per * (8 + params) <= 128 * 1024) return 8;
+    if (per * (4 + params) <= 128 * 1024) return 4;
+    if (per * (2 + params) <= 128 * 1024) return 2;
+    if (per * (1 + params) <= 160 * 1024) return 1;
+    return 0;
+}
+
+template <int FMT, int R, int QB>
+hipError_t launch_code_scan(const float* q, int64_t nq, const uint8_t* codes, int64_t n, int d, const float* ga,
+                            const float* gb, int metric, int k, int64_t id_offset, int64_t nch, float* pd, uint32_t* pi,
+                            hipStream_t st) {
+    using F = Fmt<FMT>;
+    const size_t smem = (size_t)(QB + F::kParams) * ((d + 3) & ~3) * sizeof(float);
+    auto kern = code_scan_kernel<FMT, R, QB>;
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return e;
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(codes);
+    const int rb = F::row_bytes(d);
+    const int wb = F::kWideWords * 4;
+    const int wide = addr % wb == 0 && rb % wb == 0;
+    const int narrow = addr % 4 == 0 && rb % 4 == 0;
+    hipLaunchKernelGGL(kern, dim3((unsigned)nch, (unsigned)ceil_div(nq, QB)), dim3(kScanWaves * 64), smem, st, q, nq, codes,
+                       n, d, ga, gb, metric, k, id_offset, ceil_div(n, nch), wide, narrow, pd, pi);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- tiled path
+constexpr int PBM = 128, PBN = 64, PBK = 16, PPAD = 4;
+
+// out[i][j] = the chain of query i against the reconstruction of code row j (pairwise_kernel's
+// tile and loop; IP negated).  `xvec`: 16-B loads of the queries; `cal`: a thread's four
+// dimensions of a row are one aligned load (SQ-8 4 B, SQ-16 8 B, SQ-4 2 B; RaBitQ reads the
+// byte holding its four bits either way).
+template <int FMT, bool IP>
+__global__ __launch_bounds__(256, 2) void code_pairwise_kernel(const float* __restrict__ x, int64_t n,
+                                                            const uint8_t* __restrict__ codes, int64_t m, int d,
+                                                            const float* __restrict__ ga, const float* __restrict__ gb,
+                                                            int xvec, int cal, float* __restrict__ out) {
+    using F = Fmt<FMT>;
+    __shared__ __attribute__((aligned(16))) float xs[2][PBK][PBM + PPAD];
+    __shared__ __attribute__((aligned(16))) float ys[2][PBK][PBN + PPAD];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int64_t r0 = (int64_t)blockIdx.x * PBM;
+    const int64_t c0 = (int64_t)blockIdx.y * PBN;
+
+    // this thread's code row of every slice, and its RaBitQ scale
+    const int yrow = tid >> 2, yq4 = tid & 3;
+    const bool yin = c0 + yrow < m;
+    const uint8_t* cr = codes + (yin ? c0 + yrow : 0) * (int64_t)F::row_bytes(d);
+    const float p = yin ? F::row_scale(cr, d) : 0.0f;
+
+    // x slice = 128 rows x 16 t (2 float4 per thread), y slice = 64 rows x 16 t (4 dimensions
+    // per thread, dequantised here); out-of-range rows and dimensions are 0 on both sides,
+    // which leaves every chain unchanged (fmaf(0, 0, a) == a)
+    f32x4 px[2], py;
+    auto fetch = [&](int k0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int f = tid + 256 * u, row = f >> 2, q4 = f & 3;
+            const int64_t gr = r0 + row;
+            const int t = k0 + 4 * q4;
+            if (xvec) {
+                px[u] = (gr < n && t < d) ? *reinterpret_cast<const f32x4*>(x + gr * d + t) : (f32x4){0.f, 0.f, 0.f, 0.f};
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) px[u][j] = (gr < n && t + j < d) ? x[gr * d + t + j] : 0.0f;
+            }
+        }
+        const int t = k0 + 4 * yq4;
+        py = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (yin && t < d) {
+            uint32_t lv[4] = {0u, 0u, 0u, 0u};
+            if (FMT == kRbq) {
+                const uint32_t b = cr[t >> 3] >> (t & 7);  // t % 4 == 0: the four bits share a byte
+#pragma unroll
+                for (int j = 0; j < 4; ++j) lv[j] = (b >> j) & 1u;
+            } else if (cal && t + 4 <= d) {
+                if (FMT == kSq8) {
+                    const uint32_t w[1] = {*reinterpret_cast<const uint32_t*>(cr + t)};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) lv[j] = Fmt<kSq8>::level(w, j);
+                } else if (FMT == kSq16) {
+                    const uint2 v = *reinterpret_cast<const uint2*>(cr + 2 * t);
+                    const uint32_t w[2] = {v.x, v.y};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) lv[j] = Fmt<kSq16>::level(w, j);
+                } else {
+                    const uint32_t w[1] = {*reinterpret_cast<const uint16_t*>(cr + (t >> 1))};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) lv[j] = Fmt<kSq4>::level(w, j);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (t + j < d) lv[j] = F::level_at(cr, t + j);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (t + j < d) {
+                    const float a = ga ? ga[t + j] : 0.0f;
+                    const float b = FMT != kRbq ? gb[t + j] : 0.0f;
+                    py[j] = F::dequant(lv[j], a, b, p);
+                }
+            }
+        }
+    };
+    auto stash = [&](int b) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int f = tid + 256 * u, row = f >> 2, q4 = f & 3;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) xs[b][4 * q4 + j][row] = px[u][j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ys[b][4 * yq4 + j][yrow] = py[j];
+    };
+
+    // scalar fp32 chains: packed fp32 math must not consume LDS-loaded registers (DESIGN.md §8,
+    // tools/isa_audit.py)
+    float acc[8][4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i][0] = acc[i][1] = acc[i][2] = acc[i][3] = 0.0f;
+
+    fetch(0);
+    stash(0);
+    __syncthreads();
+    int b = 0;
+    for (int k0 = 0; k0 < d; k0 += PBK) {
+        const bool more = k0 + PBK < d;
+        if (more) fetch(k0 + PBK);
+        // by 8, not 16: fully unrolled, a slice's LDS reads are hoisted into 256 VGPRs (one wave
+        // per SIMD; scratch under a two-wave bound); by 8 it is 77-79 VGPRs at the same speed
+#pragma unroll 8
+        for (int t = 0; t < PBK; ++t) {
+            const f32x4 xa = *reinterpret_cast<const f32x4*>(&xs[b][t][ty * 8]);
+            const f32x4 xb = *reinterpret_cast<const f32x4*>(&xs[b][t][ty * 8 + 4]);
+            const f32x4 yv = *reinterpret_cast<const f32x4*>(&ys[b][t][tx * 4]);
+            const float xv[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+            const float yy[4] = {yv.x, yv.y, yv.z, yv.w};
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (IP) {
+                        acc[i][j] = __builtin_fmaf(xv[i], yy[j], acc[i][j]);
+                    } else {
+                        const float df = __fsub_rn(xv[i], yy[j]);
+                        acc[i][j] = __builtin_fmaf(df, df, acc[i][j]);
+                    }
+                }
+            }
+        }
+        if (more) {
+            stash(b ^ 1);
+            __syncthreads();
+            b ^= 1;
+        }
+    }
+    const int64_t gc = c0 + tx * 4;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int64_t gr = r0 + ty * 8 + i;
+        if (gr >= n) continue;
+        f32x4 v = {acc[i][0], acc[i][1], acc[i][2], acc[i][3]};
+        if (IP) v = -v;
+        float* o = out + gr * m + gc;
+        if ((m & 3) == 0 && gc + 3 < m) {
+            *reinterpret_cast<f32x4*>(o) = v;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (gc + j < m) o[j] = v[j];
+        }
+    }
+}
+
+template <int FMT>
+hipError_t launch_code_tiled(const float* q, int64_t nq, const uint8_t* codes, int64_t n, int d, const float* ga,
+                             const float* gb, int metric, int k, int64_t id_offset, void* ws, float* dists, uint32_t* ids,
+                             hipStream_t st) {
+    using F = Fmt<FMT>;
+    const int xvec = (d % 4) == 0 && ((uintptr_t)q % 16) == 0;
+    const int rb = F::row_bytes(d);
+    const int lb = FMT == kSq8 ? 4 : FMT == kSq16 ? 8 : FMT == kSq4 ? 2 : 1;  // bytes of four dimensions
+    const int cal = (uintptr_t)codes % lb == 0 && rb % lb == 0;
+    const bool ip = metric == MIVQ_METRIC_INNER_PRODUCT;
+    return launch_tiled_topk(nq, n, k, id_offset, ws, dists, ids, st, [&](int64_t c0, int64_t m, float* buf) {
+        const dim3 grid((unsigned)ceil_div(nq, PBM), (unsigned)ceil_div(m, PBN));
+        const uint8_t* y = codes + c0 * rb;
+        if (ip) hipLaunchKernelGGL((code_pairwise_kernel<FMT, true>), grid, dim3(256), 0, st, q, nq, y, m, d, ga, gb, xvec, cal, buf);
+        else hipLaunchKernelGGL((code_pairwise_kernel<FMT, false>), grid, dim3(256), 0, st, q, nq, y, m, d, ga, gb, xvec, cal, buf);
+        return hipGetLastError();
+    });
+}
+
+// ---------------------------------------------------------------- workspace + dispatch
+// The workspace of a code search (nq, n > 0): the tiled path's (laid out by launch_tiled_topk:
+// key block + part lists), or the streaming scan's part lists (parts, nq, k) of distances at
+// pd and ids at pi.  Never decoded rows.  QB == 0 on the streaming path: d does not fit LDS.
+struct CodeSearchLayout {
+    bool tiled;
+    int QB;
+    int64_t nch, parts;
+    size_t pd, pi, total;
+};
+
+CodeSearchLayout code_search_layout(int64_t nq, int64_t n, int d, int k, int params) {
+    CodeSearchLayout L{};
+    L.tiled = flat_use_tiled(nq, n);
+    L.QB = code_qb(d, params);
+    if (L.tiled) {
+        L.total = flat_tiled_workspace_bytes(nq, n, k);
+    } else if (L.QB > 0) {
+        // no wider than the batch: a workgroup computes all QB chains of a row, and the scan is
+        // bound by the LDS reads of the queries (nq = 1 at QB = 8: 2.5 ms per 1M x 3072 SQ-8)
+        while (L.QB > 1 && L.QB / 2 >= nq) L.QB /= 2;
+        L.nch = adc_chunks(nq, n, L.QB);
+        L.parts = L.nch * kScanWaves;
+        const size_t list = align_up((size_t)L.parts * nq * k * 4, 256);
+        L.pd = 0;
+        L.pi = list;
+        L.total = 2 * list;
+    }
+    return L;
+}
+
+// Shared body of the two entry points (arguments validated up to the format's own).
+template <int FMT>
+int code_flat_search(const char* name, const float* q, int64_t nq, const uint8_t* codes, int64_t n, int d,
+                     const float* ga, const float* gb, int metric, int k, int64_t id_offset, void* workspace,
+                     size_t workspace_bytes, float* dists, uint32_t* ids, hipStream_t st) {
+    using F = Fmt<FMT>;
+    const CodeSearchLayout L = code_search_layout(nq, n, d, k, F::kParams);
+    MIVQ_REQUIRE(workspace && workspace_bytes >= L.total, MIVQ_ERR_WORKSPACE, "%s: workspace %zu < %zu", name,
+                 workspace_bytes, L.total);
+    if (L.tiled) {
+        const hipError_t et = launch_code_tiled<FMT>(q, nq, codes, n, d, ga, gb, metric, k, id_offset, workspace, dists, ids, st);
+        if (et != hipSuccess) return set_error(MIVQ_ERR_HIP, "%s (tiled): %s", name, hipGetErrorString(et));
+        return MIVQ_OK;
+    }
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    float* pd = reinterpret_cast<float*>(ws + L.pd);
+    uint32_t* pi = reinterpret_cast<uint32_t*>(ws + L.pi);
+    hipError_t e = with_topk_regs(k, [&](auto R) {
+        return with_query_block(L.QB, [&](auto QB) {
+            return launch_code_scan<FMT, decltype(R)::value, decltype(QB)::value>(q, nq, codes, n, d, ga, gb, metric, k,
+                                                                                  id_offset, L.nch, pd, pi, st);
+        });
+    });
+    if (e != hipSuccess) return set_error(MIVQ_ERR_HIP, "%s (scan): %s", name, hipGetErrorString(e));
+    e = launch_topk_merge(pd, pi, (int)L.parts, nq, k, dists, ids, st);
+    if (e != hipSuccess) return set_error(MIVQ_ERR_HIP, "%s (merge): %s", name, hipGetErrorString(e));
+    return MIVQ_OK;
+}
+
+// The checks every code search shares with mivq_flat_search, in its order; *done is set when
+// the call is complete without a scan (nq == 0, or n == 0: sentinel lists).
+int code_search_prologue(const char* name, int64_t nq, int64_t n, int d, int params, int metric, int k, int64_t id_offset,
+                         float* dists, uint32_t* ids, hipStream_t st, bool* done) {
+    *done = false;
+    MIVQ_REQUIRE(k <= 256, MIVQ_ERR_UNSUPPORTED, "%s: k=%d > 256", name, k);
+    MIVQ_REQUIRE(metric == MIVQ_METRIC_L2 || metric == MIVQ_METRIC_INNER_PRODUCT, MIVQ_ERR_UNSUPPORTED, "%s: metric %d",
+                 name, metric);
+    MIVQ_REQUIRE(code_qb(d, params) > 0 || flat_use_tiled(nq, n), MIVQ_ERR_UNSUPPORTED, "%s: d=%d too large for LDS", name,
+                 d);
+    MIVQ_REQUIRE(id_offset >= 0 && id_offset + n <= (int64_t)kNoId, MIVQ_ERR_INVALID, "%s: ids overflow", name);
+    if (nq == 0) {
+        *done = true;
+        return MIVQ_OK;
+    }
+    MIVQ_REQUIRE(dists && ids, MIVQ_ERR_INVALID, "%s: null pointer", name);
+    if (n == 0) {
+        *done = true;
+        const hipError_t e = launch_topk_merge(nullptr, nullptr, 0, nq, k, dists, ids, st);
+        if (e != hipSuccess) return set_error(MIVQ_ERR_HIP, "%s(empty): %s", name, hipGetErrorString(e));
+    }
+    return MIVQ_OK;
+}
+
+}  // namespace
+}  // namespace mivq
+
+using namespace mivq;
+
+extern "C" size_t mivq_sq_flat_search_workspace_bytes(int64_t nq, int64_t n, int32_t d, int32_t k) {
+    if (nq <= 0 || n <= 0 || d <= 0 || k <= 0) return 0;
+    return code_search_layout(nq, n, d, k, 2).total;
+}
+
+extern "C" size_t mivq_rabitq_flat_search_workspace_bytes(int64_t nq, int64_t n, int32_t d, int32_t k) {
+    if (nq <= 0 || n <= 0 || d <= 0 || k <= 0) return 0;
+    return code_search_layout(nq, n, d, k, 1).total;
+}
+
+extern "C" int mivq_sq_flat_search(const float* q, int64_t nq, const void* codes, int64_t n, int32_t d, const float* lo,
+                                   const float* den, int32_t nbits, int32_t metric, int32_t k, int64_t id_offset,
+                                   void* workspace, size_t workspace_bytes, float* dists, uint32_t* ids, void* stream) {
+    MIVQ_REQUIRE(nq >= 0 && n >= 0 && d > 0 && k > 0, MIVQ_ERR_INVALID, "sq_flat_search: bad sizes");
+    MIVQ_REQUIRE(nbits == 4 || nbits == 8 || nbits == 16, MIVQ_ERR_INVALID, "num_bits must be 4, 8, or 16, got %d", nbits);
+    hipStream_t st = as_stream(stream);
+    bool done = false;
+    const int rc = code_search_prologue("sq_flat_search", nq, n, d, 2, metric, k, id_offset, dists, ids, st, &done);
+    if (rc != MIVQ_OK || done) return rc;
+    MIVQ_REQUIRE(q && codes && lo && den, MIVQ_ERR_INVALID, "sq_flat_search: null pointer");
+    MIVQ_REQUIRE(nbits != 16 || reinterpret_cast<uintptr_t>(codes) % 2 == 0, MIVQ_ERR_INVALID,
+                 "sq_flat_search: 16-bit codes must be 2-byte aligned");
+    const uint8_t* c = static_cast<const uint8_t*>(codes);
+    if (nbits == 4)
+        return code_flat_search<kSq4>("sq_flat_search", q, nq, c, n, d, den, lo, metric, k, id_offset, workspace,
+                                      workspace_bytes, dists, ids, st);
+    if (nbits == 8)
+        return code_flat_search<kSq8>("sq_flat_search", q, nq, c, n, d, den, lo, metric, k, id_offset, workspace,
+                                      workspace_bytes, dists, ids, st);
+    return code_flat_search<kSq16>("sq_flat_search", q, nq, c, n, d, den, lo, metric, k, id_offset, workspace,
+                                   workspace_bytes, dists, ids, st);
+}
+
+extern "C" int mivq_rabitq_flat_search(const float* q, int64_t nq, const uint8_t* codes, int64_t n, int32_t d,
+                                       const float* centroid, int32_t metric, int32_t k, int64_t id_offset, void* workspace,
+                                       size_t workspace_bytes, float* dists, uint32_t* ids, void* stream) {
+    MIVQ_REQUIRE(nq >= 0 && n >= 0 && d > 0 && k > 0, MIVQ_ERR_INVALID, "rabitq_flat_search: bad sizes");
+    hipStream_t st = as_stream(stream);
+    bool done = false;
+    const int rc = code_search_prologue("rabitq_flat_search", nq, n, d, 1, metric, k, id_offset, dists, ids, st, &done);
+    if (rc != MIVQ_OK || done) return rc;
+    MIVQ_REQUIRE(q && codes, MIVQ_ERR_INVALID, "rabitq_flat_search: null pointer");
+    return code_flat_search<kRbq>("rabitq_flat_search", q, nq, codes, n, d, centroid, nullptr, metric, k, id_offset,
+                                  workspace, workspace_bytes, dists, ids, st);
+}

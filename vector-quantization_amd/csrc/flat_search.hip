@@ -109,9 +109,14 @@ hipError_t launch_flat(const float* q, int64_t nq, const float* x, int64_t n, in
     return hipGetLastError();
 }
 
+}  // namespace
+
 // The tiled path (pairwise chains on packed VALU + segmented top-k) wins once there are
 // enough queries to fill a 128-row tile; the streaming scan keeps the small-batch cases.
+// (Shared with code_search.hip, declared in topk.h.)
 bool flat_use_tiled(int64_t nq, int64_t n) { return nq >= 16 && n >= 4096; }
+
+namespace {
 
 // The workspace of mivq_flat_search (nq, n > 0): the tiled path's (laid out by
 // launch_tiled_topk), or the streaming scan's part lists (parts, nq, k) of distances at pd and

@@ -80,6 +80,11 @@ SIGNATURES = {
                                    _vp]),
     "mivq_flat_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "mivq_flat_search": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _sz, _vp, _vp, _vp]),
+    "mivq_sq_flat_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "mivq_sq_flat_search": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _sz, _vp, _vp,
+                                       _vp]),
+    "mivq_rabitq_flat_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "mivq_rabitq_flat_search": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _i64, _vp, _sz, _vp, _vp, _vp]),
     "mivq_topk_merge": (_c.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "mivq_pairwise_distances": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp]),
     "mivq_topk_rows": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp]),
@@ -535,6 +540,65 @@ def flat_search(q: torch.Tensor, x: torch.Tensor, k: int, metric: int = METRIC_L
     ws = workspace(nb, q.device)
     _call("mivq_flat_search", _ptr(q), nq, _ptr(x), n, d, metric, k, id_offset, _ptr(ws), ws.numel(),
           _ptr(dists), _ptr(ids), _stream())
+    return dists, ids
+
+
+def _sq_code_check(codes: torch.Tensor, d: int, nbits: int, what: str) -> None:
+    want = {4: ((d + 1) // 2, (torch.uint8,)), 8: (d, (torch.uint8,)), 16: (d, (torch.int16, torch.uint16))}
+    if nbits not in want:
+        raise ValueError(f"num_bits must be 4, 8, or 16, got {nbits}")
+    width, dtypes = want[nbits]
+    if not isinstance(codes, torch.Tensor) or codes.dim() != 2 or codes.shape[1] != width or codes.dtype not in dtypes:
+        raise ValueError(f"{what}: {nbits}-bit codes of d={d} must be (n, {width}) {dtypes[0]}, "
+                         f"got {tuple(getattr(codes, 'shape', ()))} {getattr(codes, 'dtype', type(codes))}")
+
+
+def sq_flat_search(q: torch.Tensor, codes: torch.Tensor, d: int, lo: torch.Tensor, den: torch.Tensor, nbits: int,
+                   k: int, metric: int = METRIC_L2, id_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact top-k over SQ codes without decoding them (mivq_sq_flat_search): the same
+    (dists f32 (nq, k), ids int32 (nq, k) holding uint32 ids) as flat_search(q, sq_decode(codes))."""
+    _sq_code_check(codes, d, nbits, "sq_flat_search")
+    if not codes.is_contiguous() or not codes.is_cuda:
+        raise ValueError("codes must be a contiguous device tensor")
+    _check(q, "q", torch.float32, 2)
+    _check(lo, "lo", torch.float32, 1)
+    _check(den, "den", torch.float32, 1)
+    if lo.numel() != d or den.numel() != d:
+        raise ValueError(f"sq_flat_search: min/max have {lo.numel()}/{den.numel()} entries, expected d={d}")
+    if q.shape[1] != d:
+        raise ValueError(f"codes have d={d}, queries d={q.shape[1]}")
+    nq, n = q.shape[0], codes.shape[0]
+    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+    ws = workspace(load_library().mivq_sq_flat_search_workspace_bytes(nq, n, d, k), q.device)
+    _call("mivq_sq_flat_search", _ptr(q), nq, _ptr(codes), n, d, _ptr(lo), _ptr(den), nbits, metric, k, id_offset,
+          _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids), _stream())
+    return dists, ids
+
+
+def rabitq_flat_search(q: torch.Tensor, codes: torch.Tensor, d: int, centroid: Optional[torch.Tensor], k: int,
+                       metric: int = METRIC_L2, id_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact top-k over RaBitQ-1 codes without decoding them (mivq_rabitq_flat_search): the same
+    result as flat_search(q, rabitq_decode(codes)); not the estimator search rabitq_search."""
+    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.uint8 or codes.dim() != 2:
+        raise ValueError(f"rabitq_flat_search: codes must be a 2-D uint8 tensor, got "
+                         f"{tuple(getattr(codes, 'shape', ()))} {getattr(codes, 'dtype', type(codes))}")
+    if codes.shape[1] != rabitq_code_size(d):
+        raise ValueError(f"codes have {codes.shape[1]} bytes per row, expected {rabitq_code_size(d)}")
+    _check(codes, "codes", torch.uint8, 2)
+    _check(q, "q", torch.float32, 2)
+    if centroid is not None:
+        _check(centroid, "centroid", torch.float32, 1)
+        if centroid.numel() != d:
+            raise ValueError(f"rabitq_flat_search: centroid has {centroid.numel()} entries, expected d={d}")
+    if q.shape[1] != d:
+        raise ValueError(f"codes have d={d}, queries d={q.shape[1]}")
+    nq, n = q.shape[0], codes.shape[0]
+    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+    ws = workspace(load_library().mivq_rabitq_flat_search_workspace_bytes(nq, n, d, k), q.device)
+    _call("mivq_rabitq_flat_search", _ptr(q), nq, _ptr(codes), n, d, _ptr(centroid), metric, k, id_offset, _ptr(ws),
+          ws.numel(), _ptr(dists), _ptr(ids), _stream())
     return dists, ids
 
 

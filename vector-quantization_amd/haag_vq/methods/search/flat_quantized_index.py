@@ -11,8 +11,11 @@ bytes, ``save`` / ``load`` round-trip the index.  The reference decodes every co
   the codes (``mivq_adc_search``).  sum_m ||q_m - c_{m,code_m}||^2 equals ||q - x_hat||^2
   (OPQ: for the rotated query, which the orthonormal rotation preserves), so the ranking is
   the reference's up to fp32 rounding on near-ties, without materialising x_hat.
-* other quantizers (SQ, RaBitQ, ...) are decoded on the device and searched exactly
-  (``mivq_flat_search``).
+* SQ codes of an f32 fit and RaBitQ-1 codes are searched exactly as they are
+  (``mivq_sq_flat_search`` / ``mivq_rabitq_flat_search``: dequantised in registers, the ids and
+  distances of decode + ``mivq_flat_search`` bit for bit, no fp32 copy of the database).
+* other quantizers (f64-fitted SQ, Extended RaBitQ, ...) are decoded on the device and searched
+  exactly (``mivq_flat_search``).
 
 Ties are broken by the smaller id.  Saved indices are ``.npz`` archives of plain arrays
 (loaded with ``allow_pickle=False``).
@@ -65,6 +68,15 @@ def search_codes(model: BaseQuantizer, codes, Q, k: int, metric: str = "l2",
         u8 = cd if pq.B == 8 else _native.pq_unpack(cd, pq.M, pq.B)
         lut = _native.adc_lut(Qd, pq.centroids_device, pq.B, mt)
         d, i = _native.adc_search(lut, u8, k, pq.B, id_offset=id_offset)
+    elif isinstance(model, ScalarQuantizer) and model.min is not None and np.asarray(model.min).dtype == np.float32:
+        # f32-fitted SQ: the codes are scanned as they are (an f64 fit decodes in f64 and rounds
+        # to f32 afterwards, which the f32 dequantisation of the kernel does not reproduce)
+        lo, den = model._params(torch.float32)
+        d, i = _native.sq_flat_search(Qd, cd.contiguous(), len(model.min), lo, den, model.num_bits, k, mt,
+                                      id_offset=id_offset)
+    elif isinstance(model, RaBitQuantizer) and model.rabitq is not None:
+        d, i = _native.rabitq_flat_search(Qd, _arrays.to_device(cd, torch.uint8).contiguous(), model.rabitq.d, None, k,
+                                          mt, id_offset=id_offset)
     else:
         xh = model.decompress(cd)
         xh = _arrays.to_device(xh, torch.float32)
