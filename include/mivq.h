@@ -141,6 +141,24 @@ int mivq_sq_decode_f32(const void* codes, int64_t n, int32_t d, const float* lo,
 int mivq_sq_decode_f64(const void* codes, int64_t n, int32_t d, const double* lo,
                        const double* den, int32_t nbits, double* out, void* stream);
 
+/* ------------------------------------------------------ LVQ (1..8 bits, per-vector range)
+ * Replaces LVQQuantizer.fit / compress / decompress (lvq_quantization.py:42-142) bit-for-bit,
+ * fp32, one rounding per step; L = 2^nbits - 1, nbits in [1, 8] (else MIVQ_ERR_INVALID).
+ *   column_mean: mean_t = (x_0t + x_1t + ... in ascending row order) / (float)n, what numpy's
+ *                X.mean(axis=0) gives for a C-contiguous f32 array (the quantizer's mu); n >= 1.
+ *   encode: r_t = x_t - mu_t, lo = min r, hi = max r, delta = (hi - lo) == 0 ? FLT_MIN :
+ *           (hi - lo) / L, idx_t = clip((int)rint((r_t - lo) / delta), 0, L), rint half to even.
+ *   Code row = ceil(d*nbits/8) index bytes (idx_t in bits [t*nbits, (t+1)*nbits) of the row's
+ *           bit stream, MSB-first from byte 0 = np.packbits(bitorder='big'), padding bits 0)
+ *           followed by f32 lo and f32 delta, little-endian; code_size = ceil(d*nbits/8) + 8.
+ *   decode: out_t = (lo + (float)idx_t * delta) + mu_t.
+ * Inputs are finite; a row holding NaN encodes to unspecified bytes of its own row. */
+int mivq_column_mean(const float* x, int64_t n, int32_t d, float* mean, void* stream);
+int mivq_lvq_encode(const float* x, int64_t n, int32_t d, const float* mu, int32_t nbits,
+                    uint8_t* codes, void* stream);
+int mivq_lvq_decode(const uint8_t* codes, int64_t n, int32_t d, const float* mu, int32_t nbits,
+                    float* out, void* stream);
+
 /* ------------------------------------------------------ RaBitQ (1 bit)
  * Replaces faiss.RaBitQuantizer.compute_codes / decode (rabit_quantization.py:20-29).
  * Code row = ceil(d/8) sign bytes (bit j of dim j = (x_j - c_j) > 0, LSB-first) followed by
@@ -241,6 +259,15 @@ int mivq_rabitq_flat_search(const float* q, int64_t nq, const uint8_t* codes, in
                             const float* centroid, int32_t metric, int32_t k, int64_t id_offset,
                             void* workspace, size_t workspace_bytes, float* dists, uint32_t* ids,
                             void* stream);
+/* The same over LVQ codes: rows and mu as in mivq_lvq_decode, x^_t = (lo + idx_t * delta) + mu_t
+ * with the row's lo and delta from its trailer; dists and ids bit-identical to mivq_lvq_decode +
+ * mivq_flat_search.  8-byte aligned rows (code_size % 8 == 0, aligned base) with an even nbits
+ * are read with 8-byte loads, 4-byte aligned rows with 4-byte loads, others byte-wise. */
+size_t mivq_lvq_flat_search_workspace_bytes(int64_t nq, int64_t n, int32_t d, int32_t k);
+int mivq_lvq_flat_search(const float* q, int64_t nq, const uint8_t* codes, int64_t n, int32_t d,
+                         const float* mu, int32_t nbits, int32_t metric, int32_t k,
+                         int64_t id_offset, void* workspace, size_t workspace_bytes, float* dists,
+                         uint32_t* ids, void* stream);
 /* Merges `parts` sorted (nq, k) lists laid out (parts, nq, k) into one sorted (nq, k) list
  * with the same (dist, id) order — the on-device merge after the RCCL all-gather. */
 int mivq_topk_merge(const float* dists_in, const uint32_t* ids_in, int32_t parts, int64_t nq,

@@ -1,18 +1,20 @@
-// code_search.hip — exact flat search over SQ-4/8/16 and RaBitQ-1 codes on gfx950.
+// code_search.hip — exact flat search over SQ-4/8/16, RaBitQ-1 and LVQ-1..8 codes on gfx950.
 //
 // The code-domain siblings of flat_search.hip's two paths: the packed codes are read once and
 // dequantised in registers, so no fp32 copy of the database exists at any point.  Every
 // reconstruction x^_t is the float the decode kernels write (sq.hip sq_decode_kernel,
-// rabitq.hip rabitq_decode_kernel; one rounding per step, -ffp-contract=off) and the distances
-// are the chains of mivq_flat_search, so ids and distances are bit-identical to
-// decode + mivq_flat_search.
+// rabitq.hip rabitq_decode_kernel, lvq.hip lvq_decode_kernel; one rounding per step,
+// -ffp-contract=off) and the distances are the chains of mivq_flat_search, so ids and distances
+// are bit-identical to decode + mivq_flat_search.
 //
 //   code_scan_kernel      the flat_scan_kernel shape: QB queries and the per-dimension
-//                         parameters (SQ: den, lo; RaBitQ: centroid) in LDS, lane = database
-//                         row, WaveTopK lists merged by launch_topk_merge.  A row is read with
-//                         16-B (RaBitQ: 8-B) loads while whole loads fit and the rows are that
-//                         aligned, then 4-B loads, then single code elements (the tail, and
-//                         every row of an unaligned database).
+//                         parameters (SQ: den, lo; RaBitQ: centroid; LVQ: mu) in LDS, lane =
+//                         database row, WaveTopK lists merged by launch_topk_merge.  A row is
+//                         read with 16-B (RaBitQ, LVQ: 8-B) loads while whole loads fit and the
+//                         rows are that aligned, then 4-B loads, then single code elements (the
+//                         tail, and every row of an unaligned database).  An LVQ row is an
+//                         MSB-first B-bit stream: 32 dimensions are B whole words, read as one
+//                         unit, byte-swapped, the fields that cross a word funnel-shifted.
 //   code_pairwise_kernel  the pairwise_kernel shape (128 x 64 tile, k-slices of 16 in LDS) as
 //                         launch_tiled_topk's TileFn: the database side of a slice is fetched
 //                         as codes and dequantised before it is stashed.
@@ -26,30 +28,41 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-enum : int { kSq4 = 0, kSq8 = 1, kSq16 = 2, kRbq = 3 };
+// kLvq + B - 1 is LVQ with B bits per dimension, B = 1 .. 8
+enum : int { kSq4 = 0, kSq8 = 1, kSq16 = 2, kRbq = 3, kLvq = 4 };
 
 // ---------------------------------------------------------------- code formats
 template <int FMT>
 struct Fmt {
-    // dims per 32-bit word of codes
+    static constexpr bool kIsLvq = FMT >= kLvq;
+    static constexpr int kB = kIsLvq ? FMT - kLvq + 1 : 0;  // LVQ bits per dimension
+    static constexpr uint32_t kMask = (1u << kB) - 1u;
+    // dims per 32-bit word of codes (LVQ: per unit of kB words)
     static constexpr int kWordDims = FMT == kSq4 ? 8 : FMT == kSq8 ? 4 : FMT == kSq16 ? 2 : 32;
-    // words per wide load of the scan (16 B; 8 B for RaBitQ, whose rows of d % 64 == 0 are 8-B aligned)
-    static constexpr int kWideWords = FMT == kRbq ? 2 : 4;
-    // per-dimension parameter arrays: SQ {den, lo}, RaBitQ {centroid}
-    static constexpr int kParams = FMT == kRbq ? 1 : 2;
+    // words per wide load of the scan (16 B; 8 B for RaBitQ and LVQ, whose rows of d % 64 == 0
+    // are 8-B aligned: the 8-byte trailer follows a multiple of 8 code bytes)
+    static constexpr int kWideWords = FMT == kRbq || kIsLvq ? 2 : 4;
+    // per-dimension parameter arrays: SQ {den, lo}, RaBitQ {centroid}, LVQ {mu}
+    static constexpr int kParams = FMT == kRbq || kIsLvq ? 1 : 2;
     static constexpr float kLevels = FMT == kSq4 ? 15.0f : FMT == kSq8 ? 255.0f : 65535.0f;
     static constexpr float kRcpLevels = 1.0f / kLevels;  // RN(1 / L)
 
     __host__ __device__ static int code_bytes(int d) {
+        if (kIsLvq) return (int)(((int64_t)d * kB + 7) / 8);
         return FMT == kSq4 ? (d + 1) / 2 : FMT == kSq8 ? d : FMT == kSq16 ? 2 * d : (d + 7) / 8;
     }
-    __host__ __device__ static int row_bytes(int d) { return code_bytes(d) + (FMT == kRbq ? 8 : 0); }
+    __host__ __device__ static int row_bytes(int d) { return code_bytes(d) + (FMT == kRbq || kIsLvq ? 8 : 0); }
     // byte offset of dimension t (a multiple of kWordDims) in a row
     __device__ static int byte_of(int t) { return FMT == kSq4 ? t >> 1 : FMT == kSq8 ? t : FMT == kSq16 ? 2 * t : t >> 3; }
 
     // level (SQ) / sign bit (RaBitQ) of dimension u of the little-endian words w[]
     template <int NW>
     __device__ __forceinline__ static uint32_t level(const uint32_t (&w)[NW], int u) {
+        if (kIsLvq) {  // w[]: the unit's words byte-swapped, field u at bits [u kB, (u + 1) kB) from the top
+            const int o = u * kB, wi = o >> 5, end = (o & 31) + kB;
+            if (end <= 32) return (w[wi] >> (32 - end)) & kMask;
+            return ((w[wi] << (end - 32)) | (w[wi + 1 < NW ? wi + 1 : wi] >> (64 - end))) & kMask;
+        }
         if (FMT == kSq8) return (w[u >> 2] >> (8 * (u & 3))) & 0xFFu;
         if (FMT == kSq16) return (w[u >> 1] >> (16 * (u & 1))) & 0xFFFFu;
         if (FMT == kSq4) {  // even dimension in the high nibble
@@ -60,6 +73,11 @@ struct Fmt {
     }
     // the same for dimension t of row `cr`, one code element at a time
     __device__ __forceinline__ static uint32_t level_at(const uint8_t* cr, int t) {
+        if (kIsLvq) {  // the field lies in two bytes at most (the byte after the last is the trailer's)
+            const int o = t * kB, fb = o >> 3;
+            const uint32_t v = (uint32_t)cr[fb] << 8 | cr[fb + 1];
+            return (v >> (16 - (o & 7) - kB)) & kMask;
+        }
         if (FMT == kSq8) return cr[t];
         if (FMT == kSq16) return reinterpret_cast<const uint16_t*>(cr)[t];
         if (FMT == kSq4) {
@@ -70,40 +88,48 @@ struct Fmt {
     }
     // x^_t.  SQ: a = den_t, b = lo_t, fadd(fmul(fdiv(level, L), den_t), lo_t) with the division as
     // the reciprocal sequence of sq.hip's div_rn_rcp (RN(level / L) for every level 0 .. L).
-    // RaBitQ: a = c_t (0 without a centroid), p the row's fmul(fmul(fmul(0.5, mult), 2), 1/sqrt(d)).
-    __device__ __forceinline__ static float dequant(uint32_t lv, float a, float b, float p) {
-        if (FMT == kRbq) return __fadd_rn(lv ? p : -p, a);
+    // RaBitQ: a = c_t (0 without a centroid), p.x the row's fmul(fmul(fmul(0.5, mult), 2), 1/sqrt(d)).
+    // LVQ: a = mu_t, p = the row's {lo, delta}: fadd(fadd(lo, fmul(idx, delta)), mu_t).
+    __device__ __forceinline__ static float dequant(uint32_t lv, float a, float b, float2 p) {
+        if (kIsLvq) return __fadd_rn(__fadd_rn(p.x, __fmul_rn((float)lv, p.y)), a);
+        if (FMT == kRbq) return __fadd_rn(lv ? p.x : -p.x, a);
         const float f = (float)lv;
         const float q0 = __fmul_rn(f, kRcpLevels);
         const float e = __builtin_fmaf(-q0, kLevels, f);
         const float s = __builtin_fmaf(e, kRcpLevels, q0);
         return __fadd_rn(__fmul_rn(s, a), b);
     }
-    // RaBitQ: p of the row (mult is the second trailer float, read byte-wise: rows are unaligned)
-    __device__ __forceinline__ static float row_scale(const uint8_t* cr, int d) {
-        if (FMT != kRbq) return 0.0f;
-        const int nb = (d + 7) / 8;
-        uint32_t mu = 0;
+    // The row's own parameters from its trailer (read byte-wise: rows are unaligned).  RaBitQ: p
+    // in .x, from mult, the second trailer float; LVQ: {lo, delta}, the two trailer floats.
+    __device__ __forceinline__ static float2 row_scale(const uint8_t* cr, int d) {
+        if (FMT != kRbq && !kIsLvq) return make_float2(0.0f, 0.0f);
+        const int nb = code_bytes(d);
+        uint32_t u0 = 0, u1 = 0;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) mu |= (uint32_t)cr[nb + 4 + q] << (8 * q);
+        for (int q = 0; q < 4; ++q) {
+            if (kIsLvq) u0 |= (uint32_t)cr[nb + q] << (8 * q);
+            u1 |= (uint32_t)cr[nb + 4 + q] << (8 * q);
+        }
+        if (kIsLvq) return make_float2(__uint_as_float(u0), __uint_as_float(u1));
         const float inv_d_sqrt = __fdiv_rn(1.0f, sqrtf((float)d));
-        return __fmul_rn(__fmul_rn(__fmul_rn(0.5f, __uint_as_float(mu)), 2.0f), inv_d_sqrt);
+        return make_float2(__fmul_rn(__fmul_rn(__fmul_rn(0.5f, __uint_as_float(u1)), 2.0f), inv_d_sqrt), 0.0f);
     }
 };
 
 // ---------------------------------------------------------------- streaming scan
 // NW loaded words = NW * kWordDims (a multiple of 4) dimensions from t0 (a multiple of 4) on:
-// four at a time, the parameters and the queries as 16-B LDS reads.
+// four at a time, the parameters and the queries as 16-B LDS reads.  LVQ: the kB byte-swapped
+// words of one unit, 32 dimensions.
 template <int FMT, int NW, int QB>
 __device__ __forceinline__ void scan_words(const uint32_t (&w)[NW], int t0, const float* qv, int dp, const float* pa,
-                                           const float* pb, float p, bool l2, float (&dist)[QB]) {
-    constexpr int ND = NW * Fmt<FMT>::kWordDims;
+                                           const float* pb, float2 p, bool l2, float (&dist)[QB]) {
+    constexpr int ND = Fmt<FMT>::kIsLvq ? 32 : NW * Fmt<FMT>::kWordDims;
     static_assert(ND % 4 == 0, "whole groups of four dimensions");
 #pragma unroll
     for (int g = 0; g < ND; g += 4) {
         const float4 a4 = *reinterpret_cast<const float4*>(pa + t0 + g);
         float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (FMT != kRbq) b4 = *reinterpret_cast<const float4*>(pb + t0 + g);
+        if (Fmt<FMT>::kParams == 2) b4 = *reinterpret_cast<const float4*>(pb + t0 + g);
         const float x0 = Fmt<FMT>::dequant(Fmt<FMT>::level(w, g + 0), a4.x, b4.x, p);
         const float x1 = Fmt<FMT>::dequant(Fmt<FMT>::level(w, g + 1), a4.y, b4.y, p);
         const float x2 = Fmt<FMT>::dequant(Fmt<FMT>::level(w, g + 2), a4.z, b4.z, p);
@@ -147,7 +173,7 @@ __global__ __launch_bounds__(kScanWaves * 64) void code_scan_kernel(
         for (int t = tid; t < d; t += kScanWaves * 64) qv[qq * dp + t] = q[(q0 + qq) * d + t];
     for (int t = tid; t < d; t += kScanWaves * 64) {
         pa[t] = ga ? ga[t] : 0.0f;
-        if (FMT != kRbq) pb[t] = gb[t];
+        if (F::kParams == 2) pb[t] = gb[t];
     }
     __syncthreads();
     WaveTopK<R> top[QB];
@@ -173,29 +199,54 @@ __global__ __launch_bounds__(kScanWaves * 64) void code_scan_kernel(
         for (int qq = 0; qq < QB; ++qq) dist[qq] = 0.0f;
         if (valid) {
             const uint8_t* cr = codes + row * stride;
-            const float p = F::row_scale(cr, d);
+            const float2 p = F::row_scale(cr, d);
             int t = 0;
-            for (; t < twide; t += NDW) {
-                uint32_t w[F::kWideWords];
-                if constexpr (F::kWideWords == 4) {
-                    const uint4 v = *reinterpret_cast<const uint4*>(cr + F::byte_of(t));
-                    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-                } else {
-                    const uint2 v = *reinterpret_cast<const uint2*>(cr + F::byte_of(t));
-                    w[0] = v.x; w[1] = v.y;
+            if constexpr (F::kIsLvq) {
+                // whole units of 32 dimensions = kB words: 8-B loads (even kB, 8-B aligned rows) or
+                // 4-B loads; the rest of the row, and every row of an unaligned database, below
+                constexpr int B = F::kB;
+                const int tunit = narrow ? d / 32 * 32 : 0;
+                for (; t < tunit; t += 32) {
+                    uint32_t w[B];
+                    const uint8_t* cu = cr + (t >> 3) * B;
+                    if (B % 2 == 0 && wide) {
+#pragma unroll
+                        for (int i = 0; i < B / 2; ++i) {
+                            const uint2 v = reinterpret_cast<const uint2*>(cu)[i];
+                            w[2 * i] = v.x;
+                            w[2 * i + (B > 1 ? 1 : 0)] = v.y;
+                        }
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < B; ++i) w[i] = reinterpret_cast<const uint32_t*>(cu)[i];
+                    }
+#pragma unroll
+                    for (int i = 0; i < B; ++i) w[i] = __builtin_bswap32(w[i]);
+                    scan_words<FMT, B, QB>(w, t, qv, dp, pa, pb, p, l2, dist);
                 }
-                scan_words<FMT, F::kWideWords, QB>(w, t, qv, dp, pa, pb, p, l2, dist);
-            }
-            if constexpr (F::kWordDims % 4 == 0) {  // (an SQ-16 word is half a group: no 4-B step)
-                if (narrow) {
-                    for (; t + F::kWordDims <= d; t += F::kWordDims) {
-                        const uint32_t w[1] = {*reinterpret_cast<const uint32_t*>(cr + F::byte_of(t))};
-                        scan_words<FMT, 1, QB>(w, t, qv, dp, pa, pb, p, l2, dist);
+            } else {
+                for (; t < twide; t += NDW) {
+                    uint32_t w[F::kWideWords];
+                    if constexpr (F::kWideWords == 4) {
+                        const uint4 v = *reinterpret_cast<const uint4*>(cr + F::byte_of(t));
+                        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+                    } else {
+                        const uint2 v = *reinterpret_cast<const uint2*>(cr + F::byte_of(t));
+                        w[0] = v.x; w[1] = v.y;
+                    }
+                    scan_words<FMT, F::kWideWords, QB>(w, t, qv, dp, pa, pb, p, l2, dist);
+                }
+                if constexpr (F::kWordDims % 4 == 0) {  // (an SQ-16 word is half a group: no 4-B step)
+                    if (narrow) {
+                        for (; t + F::kWordDims <= d; t += F::kWordDims) {
+                            const uint32_t w[1] = {*reinterpret_cast<const uint32_t*>(cr + F::byte_of(t))};
+                            scan_words<FMT, 1, QB>(w, t, qv, dp, pa, pb, p, l2, dist);
+                        }
                     }
                 }
             }
             for (; t < d; ++t) {
-                const float xh = F::dequant(F::level_at(cr, t), pa[t], FMT != kRbq ? pb[t] : 0.0f, p);
+                const float xh = F::dequant(F::level_at(cr, t), pa[t], F::kParams == 2 ? pb[t] : 0.0f, p);
 #pragma unroll
                 for (int qq = 0; qq < QB; ++qq) {
                     if (l2) {
@@ -275,7 +326,7 @@ __global__ __launch_bounds__(256, 2) void code_pairwise_kernel(const float* __re
     const int yrow = tid >> 2, yq4 = tid & 3;
     const bool yin = c0 + yrow < m;
     const uint8_t* cr = codes + (yin ? c0 + yrow : 0) * (int64_t)F::row_bytes(d);
-    const float p = yin ? F::row_scale(cr, d) : 0.0f;
+    const float2 p = yin ? F::row_scale(cr, d) : make_float2(0.0f, 0.0f);
 
     // x slice = 128 rows x 16 t (2 float4 per thread), y slice = 64 rows x 16 t (4 dimensions
     // per thread, dequantised here); out-of-range rows and dimensions are 0 on both sides,
@@ -298,7 +349,16 @@ __global__ __launch_bounds__(256, 2) void code_pairwise_kernel(const float* __re
         py = (f32x4){0.f, 0.f, 0.f, 0.f};
         if (yin && t < d) {
             uint32_t lv[4] = {0u, 0u, 0u, 0u};
-            if (FMT == kRbq) {
+            if (F::kIsLvq) {
+                // t % 4 == 0: the four fields are 4 kB bits from a byte or half-byte boundary on,
+                // five bytes at most (those past the code bytes are the trailer's)
+                const int o = t * F::kB, fb = o >> 3;
+                uint64_t v = 0;
+#pragma unroll
+                for (int q = 0; q < (4 * F::kB + 4 + 7) / 8; ++q) v |= (uint64_t)cr[fb + q] << (32 - 8 * q);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) lv[j] = (uint32_t)(v >> (40 - (o & 7) - F::kB * (j + 1))) & F::kMask;
+            } else if (FMT == kRbq) {
                 const uint32_t b = cr[t >> 3] >> (t & 7);  // t % 4 == 0: the four bits share a byte
 #pragma unroll
                 for (int j = 0; j < 4; ++j) lv[j] = (b >> j) & 1u;
@@ -326,7 +386,7 @@ __global__ __launch_bounds__(256, 2) void code_pairwise_kernel(const float* __re
             for (int j = 0; j < 4; ++j) {
                 if (t + j < d) {
                     const float a = ga ? ga[t + j] : 0.0f;
-                    const float b = FMT != kRbq ? gb[t + j] : 0.0f;
+                    const float b = F::kParams == 2 ? gb[t + j] : 0.0f;
                     py[j] = F::dequant(lv[j], a, b, p);
                 }
             }
@@ -409,7 +469,7 @@ hipError_t launch_code_tiled(const float* q, int64_t nq, const uint8_t* codes, i
     using F = Fmt<FMT>;
     const int xvec = (d % 4) == 0 && ((uintptr_t)q % 16) == 0;
     const int rb = F::row_bytes(d);
-    const int lb = FMT == kSq8 ? 4 : FMT == kSq16 ? 8 : FMT == kSq4 ? 2 : 1;  // bytes of four dimensions
+    const int lb = FMT == kSq8 ? 4 : FMT == kSq16 ? 8 : FMT == kSq4 ? 2 : 1;  // bytes of four dimensions (SQ)
     const int cal = (uintptr_t)codes % lb == 0 && rb % lb == 0;
     const bool ip = metric == MIVQ_METRIC_INNER_PRODUCT;
     return launch_tiled_topk(nq, n, k, id_offset, ws, dists, ids, st, [&](int64_t c0, int64_t m, float* buf) {
@@ -520,6 +580,11 @@ extern "C" size_t mivq_rabitq_flat_search_workspace_bytes(int64_t nq, int64_t n,
     return code_search_layout(nq, n, d, k, 1).total;
 }
 
+extern "C" size_t mivq_lvq_flat_search_workspace_bytes(int64_t nq, int64_t n, int32_t d, int32_t k) {
+    if (nq <= 0 || n <= 0 || d <= 0 || k <= 0) return 0;
+    return code_search_layout(nq, n, d, k, 1).total;
+}
+
 extern "C" int mivq_sq_flat_search(const float* q, int64_t nq, const void* codes, int64_t n, int32_t d, const float* lo,
                                    const float* den, int32_t nbits, int32_t metric, int32_t k, int64_t id_offset,
                                    void* workspace, size_t workspace_bytes, float* dists, uint32_t* ids, void* stream) {
@@ -554,4 +619,32 @@ extern "C" int mivq_rabitq_flat_search(const float* q, int64_t nq, const uint8_t
     MIVQ_REQUIRE(q && codes, MIVQ_ERR_INVALID, "rabitq_flat_search: null pointer");
     return code_flat_search<kRbq>("rabitq_flat_search", q, nq, codes, n, d, centroid, nullptr, metric, k, id_offset,
                                   workspace, workspace_bytes, dists, ids, st);
+}
+
+extern "C" int mivq_lvq_flat_search(const float* q, int64_t nq, const uint8_t* codes, int64_t n, int32_t d, const float* mu,
+                                    int32_t nbits, int32_t metric, int32_t k, int64_t id_offset, void* workspace,
+                                    size_t workspace_bytes, float* dists, uint32_t* ids, void* stream) {
+    MIVQ_REQUIRE(nq >= 0 && n >= 0 && d > 0 && d <= (1 << 27) && k > 0, MIVQ_ERR_INVALID, "lvq_flat_search: bad sizes");
+    MIVQ_REQUIRE(nbits >= 1 && nbits <= 8, MIVQ_ERR_INVALID, "num_bits must be in [1, 8], got %d", nbits);
+    hipStream_t st = as_stream(stream);
+    bool done = false;
+    const int rc = code_search_prologue("lvq_flat_search", nq, n, d, 1, metric, k, id_offset, dists, ids, st, &done);
+    if (rc != MIVQ_OK || done) return rc;
+    MIVQ_REQUIRE(q && codes && mu, MIVQ_ERR_INVALID, "lvq_flat_search: null pointer");
+#define MIVQ_LVQ_SEARCH(B)                                                                                             \
+    case B:                                                                                                            \
+        return code_flat_search<kLvq + B - 1>("lvq_flat_search", q, nq, codes, n, d, mu, nullptr, metric, k, id_offset, \
+                                              workspace, workspace_bytes, dists, ids, st)
+    switch (nbits) {
+        MIVQ_LVQ_SEARCH(1);
+        MIVQ_LVQ_SEARCH(2);
+        MIVQ_LVQ_SEARCH(3);
+        MIVQ_LVQ_SEARCH(4);
+        MIVQ_LVQ_SEARCH(5);
+        MIVQ_LVQ_SEARCH(6);
+        MIVQ_LVQ_SEARCH(7);
+        MIVQ_LVQ_SEARCH(8);
+        default: return MIVQ_ERR_INVALID;
+    }
+#undef MIVQ_LVQ_SEARCH
 }

@@ -64,6 +64,9 @@ SIGNATURES = {
     "mivq_sq_encode_f64": (_c.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp]),
     "mivq_sq_decode_f32": (_c.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp]),
     "mivq_sq_decode_f64": (_c.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "mivq_column_mean": (_c.c_int, [_vp, _i64, _i32, _vp, _vp]),
+    "mivq_lvq_encode": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp]),
+    "mivq_lvq_decode": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp]),
     "mivq_rabitq_encode": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp]),
     "mivq_rabitq_decode": (_c.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
     "mivq_rabitq_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
@@ -85,6 +88,9 @@ SIGNATURES = {
                                        _vp]),
     "mivq_rabitq_flat_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "mivq_rabitq_flat_search": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _i64, _vp, _sz, _vp, _vp, _vp]),
+    "mivq_lvq_flat_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "mivq_lvq_flat_search": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i64, _vp, _sz, _vp, _vp,
+                                        _vp]),
     "mivq_topk_merge": (_c.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "mivq_pairwise_distances": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp]),
     "mivq_topk_rows": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp]),
@@ -393,6 +399,66 @@ def sq_decode(codes: torch.Tensor, d: int, lo: torch.Tensor, den: torch.Tensor, 
     return out
 
 
+# ----------------------------------------------------------------- LVQ
+def lvq_code_size(d: int, nbits: int) -> int:
+    return (d * nbits + 7) // 8 + 8
+
+
+def _lvq_bits_check(nbits: int) -> None:
+    if not 1 <= nbits <= 8:
+        raise ValueError(f"num_bits must be in [1, 8], got {nbits}")
+
+
+def column_mean(x: torch.Tensor) -> torch.Tensor:
+    """numpy's X.mean(axis=0) of a C-contiguous f32 array, bit for bit: the fp32 column sums in
+    ascending row order, divided by float(n)."""
+    _check(x, "x", torch.float32, 2)
+    n, d = x.shape
+    if n < 1 or d < 1:
+        raise ValueError(f"column_mean: empty input {tuple(x.shape)}")
+    out = torch.empty((d,), dtype=torch.float32, device=x.device)
+    _call("mivq_column_mean", _ptr(x), n, d, _ptr(out), _stream())
+    return out
+
+
+def lvq_encode(x: torch.Tensor, mu: torch.Tensor, nbits: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    _lvq_bits_check(nbits)
+    _check(x, "x", torch.float32, 2)
+    _check(mu, "mu", torch.float32, 1)
+    n, d = x.shape
+    if mu.numel() != d:
+        raise ValueError(f"lvq_encode: mu has {mu.numel()} entries, data has d={d}")
+    cs = lvq_code_size(d, nbits)
+    if out is None:
+        out = torch.empty((n, cs), dtype=torch.uint8, device=x.device)
+    else:
+        _check(out, "out", torch.uint8, 2)
+        if tuple(out.shape) != (n, cs):
+            raise ValueError(f"out shape {tuple(out.shape)} != {(n, cs)}")
+    _call("mivq_lvq_encode", _ptr(x), n, d, _ptr(mu), nbits, _ptr(out), _stream())
+    return out
+
+
+def _lvq_code_check(codes: torch.Tensor, d: int, nbits: int, what: str) -> None:
+    _lvq_bits_check(nbits)
+    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.uint8 or codes.dim() != 2:
+        raise ValueError(f"{what}: codes must be a 2-D uint8 tensor, got "
+                         f"{tuple(getattr(codes, 'shape', ()))} {getattr(codes, 'dtype', type(codes))}")
+    if codes.shape[1] != lvq_code_size(d, nbits):
+        raise ValueError(f"codes have {codes.shape[1]} bytes per row, expected {lvq_code_size(d, nbits)}")
+    _check(codes, "codes", torch.uint8, 2)
+
+
+def lvq_decode(codes: torch.Tensor, mu: torch.Tensor, nbits: int) -> torch.Tensor:
+    _check(mu, "mu", torch.float32, 1)
+    d = mu.numel()
+    _lvq_code_check(codes, d, nbits, "lvq_decode")
+    n = codes.shape[0]
+    out = torch.empty((n, d), dtype=torch.float32, device=codes.device)
+    _call("mivq_lvq_decode", _ptr(codes), n, d, _ptr(mu), nbits, _ptr(out), _stream())
+    return out
+
+
 # ----------------------------------------------------------------- RaBitQ
 def rabitq_code_size(d: int) -> int:
     return (d + 7) // 8 + 8
@@ -598,6 +664,25 @@ def rabitq_flat_search(q: torch.Tensor, codes: torch.Tensor, d: int, centroid: O
     ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
     ws = workspace(load_library().mivq_rabitq_flat_search_workspace_bytes(nq, n, d, k), q.device)
     _call("mivq_rabitq_flat_search", _ptr(q), nq, _ptr(codes), n, d, _ptr(centroid), metric, k, id_offset, _ptr(ws),
+          ws.numel(), _ptr(dists), _ptr(ids), _stream())
+    return dists, ids
+
+
+def lvq_flat_search(q: torch.Tensor, codes: torch.Tensor, mu: torch.Tensor, nbits: int, k: int,
+                    metric: int = METRIC_L2, id_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact top-k over LVQ codes without decoding them (mivq_lvq_flat_search): the same
+    (dists f32 (nq, k), ids int32 (nq, k) holding uint32 ids) as flat_search(q, lvq_decode(codes))."""
+    _check(mu, "mu", torch.float32, 1)
+    d = mu.numel()
+    _lvq_code_check(codes, d, nbits, "lvq_flat_search")
+    _check(q, "q", torch.float32, 2)
+    if q.shape[1] != d:
+        raise ValueError(f"codes have d={d}, queries d={q.shape[1]}")
+    nq, n = q.shape[0], codes.shape[0]
+    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+    ws = workspace(load_library().mivq_lvq_flat_search_workspace_bytes(nq, n, d, k), q.device)
+    _call("mivq_lvq_flat_search", _ptr(q), nq, _ptr(codes), n, d, _ptr(mu), nbits, metric, k, id_offset, _ptr(ws),
           ws.numel(), _ptr(dists), _ptr(ids), _stream())
     return dists, ids
 

@@ -3,8 +3,9 @@
 Same dispatch as /root/reference/src/haag_vq/benchmarks/method_registry.py:12-61:
 PQ / OPQ use B = 8 and M = largest_divisor_leq(D, round(bpd*D) // 8); SQ uses 4 bits for
 bpd <= 4.5, 8 for bpd <= 12, else 16; ``rabitq`` routes to the multi-bit Extended RaBitQ
-(method_registry_saq.py:45-48).  The SAQ-engine / LVQ / rank-aware research methods are out
-of scope of the MI355X build and raise ValueError.
+(method_registry_saq.py:45-48) and ``lvq`` to the single-level LVQ with round(bpd) bits
+(method_registry_saq.py:49-52).  The SAQ-engine / rank-aware research methods are out of scope
+of the MI355X build and raise ValueError.
 """
 
 from __future__ import annotations
@@ -44,7 +45,7 @@ def build_faiss_quantizer(method: str, bpd: float, D: int) -> FaissQuantizerAdap
     raise ValueError(f"Unknown faiss method: {method!r}")
 
 
-SUPPORTED_SAQ_METHODS = ("rabitq",)
+SUPPORTED_SAQ_METHODS = ("rabitq", "lvq")
 SAQ_METHODS = ("saq_paper", "ours", "ours_exact", "rabitq", "lvq",
                "rankaware", "perdim_mse", "rankaware_exact", "perdim_mse_exact")
 ALL_METHODS = FAISS_METHODS + SAQ_METHODS
@@ -54,6 +55,9 @@ def build_saq_quantizer(method: str, bpd: float, D: int):
     if method == "rabitq":
         from haag_vq.methods.extended_rabitq import ExtendedRaBitQuantizer
         return FaissQuantizerAdapter(ExtendedRaBitQuantizer(num_bits=int(round(bpd))))
+    if method == "lvq":
+        from haag_vq.methods.lvq_quantization import LVQQuantizer
+        return FaissQuantizerAdapter(LVQQuantizer(num_bits=int(round(bpd))))
     if method in SAQ_METHODS:
         raise ValueError(f"{method!r} is a SAQ-study research method, out of scope of the MI355X build")
     raise ValueError(f"Unknown SAQ-study method: {method!r}")

@@ -27,7 +27,7 @@ class Quantizer(Protocol):
 
 
 class FaissQuantizerAdapter:
-    """Adapts a BaseQuantizer (PQ / OPQ / SQ / RaBitQ / ExtRaBitQ) to the Quantizer protocol."""
+    """Adapts a BaseQuantizer (PQ / OPQ / SQ / RaBitQ / ExtRaBitQ / LVQ) to the Quantizer protocol."""
 
     def __init__(self, quantizer: BaseQuantizer) -> None:
         self._q = quantizer

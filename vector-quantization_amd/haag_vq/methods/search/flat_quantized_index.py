@@ -14,6 +14,9 @@ bytes, ``save`` / ``load`` round-trip the index.  The reference decodes every co
 * SQ codes of an f32 fit and RaBitQ-1 codes are searched exactly as they are
   (``mivq_sq_flat_search`` / ``mivq_rabitq_flat_search``: dequantised in registers, the ids and
   distances of decode + ``mivq_flat_search`` bit for bit, no fp32 copy of the database).
+* LVQ codes likewise (``mivq_lvq_flat_search``: the MSB-first bit stream and the per-row
+  ``lo`` / ``delta`` read in the scan, the ids and distances of ``mivq_lvq_decode`` +
+  ``mivq_flat_search`` bit for bit).
 * other quantizers (f64-fitted SQ, Extended RaBitQ, ...) are decoded on the device and searched
   exactly (``mivq_flat_search``).
 
@@ -32,6 +35,7 @@ import torch
 from ... import _arrays, _native
 from ..base_quantizer import BaseQuantizer
 from ..base_search_index import BaseSearchIndex
+from ..lvq_quantization import LVQQuantizer
 from ..optimized_product_quantization import OptimizedProductQuantizer, OPQHandle
 from ..product_quantization import ProductQuantizer
 from ..rabit_quantization import RaBitQuantizer
@@ -77,6 +81,9 @@ def search_codes(model: BaseQuantizer, codes, Q, k: int, metric: str = "l2",
     elif isinstance(model, RaBitQuantizer) and model.rabitq is not None:
         d, i = _native.rabitq_flat_search(Qd, _arrays.to_device(cd, torch.uint8).contiguous(), model.rabitq.d, None, k,
                                           mt, id_offset=id_offset)
+    elif isinstance(model, LVQQuantizer) and model.mu is not None:
+        d, i = _native.lvq_flat_search(Qd, _arrays.to_device(cd, torch.uint8).contiguous(), model._mu_device(),
+                                       model.num_bits, k, mt, id_offset=id_offset)
     else:
         xh = model.decompress(cd)
         xh = _arrays.to_device(xh, torch.float32)
@@ -125,6 +132,8 @@ def quantizer_state(q: BaseQuantizer) -> dict:
         return dict(qtype=np.array("sq"), num_bits=np.array(q.num_bits), min=np.asarray(q.min), max=np.asarray(q.max))
     if isinstance(q, RaBitQuantizer):
         return dict(qtype=np.array("rabitq"), metric_type=np.array(int(q.metric_type)), d=np.array(q.rabitq.d))
+    if isinstance(q, LVQQuantizer):
+        return dict(qtype=np.array("lvq"), num_bits=np.array(q.num_bits), mu=np.asarray(q.mu, dtype=np.float32))
     raise ValueError(f"save(): unsupported quantizer {type(q).__name__}")
 
 
@@ -149,6 +158,9 @@ def quantizer_from_state(z) -> BaseQuantizer:
         from ...utils.faiss_utils import MetricType
         q = RaBitQuantizer(metric_type=MetricType(int(z["metric_type"])))
         q.fit(np.empty((0, int(z["d"])), dtype=np.float32))
+    elif qt == "lvq":
+        q = LVQQuantizer(num_bits=int(z["num_bits"]))
+        q.mu = np.array(z["mu"])
     else:
         raise ValueError(f"load(): unknown quantizer type {qt!r}")
     return q

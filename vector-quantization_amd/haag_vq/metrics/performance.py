@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from haag_vq.methods.base_quantizer import BaseQuantizer
+from haag_vq.methods.lvq_quantization import LVQQuantizer
 from haag_vq.methods.rabit_quantization import RaBitQuantizer
 from haag_vq.utils.faiss_export import query_codebook
 
@@ -66,14 +67,15 @@ def device_encode_roofline(model: BaseQuantizer, X, reps: int = 3) -> Dict[str, 
 
 def measure_qps(queries, *, model: Optional[BaseQuantizer] = None, codebook_vectors: Optional[np.ndarray] = None,
                 codebook_path: Optional[str] = None, repeats: int = 3, topk: int = 1) -> Dict[str, float]:
-    """Reference "QPS" proxy: codebook query (PQ-like / SQ) or compress(queries) (RaBitQ)."""
+    """Reference "QPS" proxy: codebook query (PQ-like / SQ) or compress(queries) (RaBitQ, and LVQ,
+    which has no codebook either)."""
     queries = np.asarray(queries, dtype=np.float32)
     if queries.ndim == 1:
         queries = queries.reshape(1, -1)
     if queries.size == 0:
         raise ValueError("No queries provided for QPS measurement")
     runs = max(1, repeats)
-    if isinstance(model, RaBitQuantizer):
+    if isinstance(model, (RaBitQuantizer, LVQQuantizer)):
         def once():
             model.compress(queries)
     else:
