@@ -327,6 +327,33 @@ int mivq_ivfpq_search(const float* lut, int64_t nq, int32_t M, int32_t nbits, co
                       int32_t metric, int32_t k, void* workspace, size_t workspace_bytes,
                       float* dists, uint32_t* ids, void* stream);
 
+/* ------------------------------------------------------ IVF over RaBitQ-1 codes
+ * Replaces faiss IVF{nlist},RaBitQ behind RaBitQIVFIndex (methods/search/rabitq_ivf_index.py).
+ * mivq_ivf_rabitq_encode: row i gets the code row of mivq_rabitq_encode with centroid =
+ * coarse[assign[i]] (same layout, bit-identical, factors included; against the oracle the
+ * factors agree within 1e-5 relative, as for mivq_rabitq_encode).  coarse: (nlist, d);
+ * assign[i] >= nlist is undefined behaviour (as for mivq_ivf_residuals). */
+int mivq_ivf_rabitq_encode(const float* x, int64_t n, int32_t d, const float* coarse,
+                           int32_t nlist, const uint32_t* assign, int32_t metric, uint8_t* codes,
+                           void* stream);
+/* Estimator search over the probed lists.  probe_l (nq, nprobe): list ids, 0xFFFFFFFF slots are
+ * skipped; offsets (nlist + 1) int64, list_codes (n, code_size), list_ids (n,) in bucket order,
+ * all on the device.  For every probed pair (query a, list l) and row i of the list the key is
+ * oracle_rabitq_est of that code with centroid = coarse[l] (the query residual q_a - coarse[l]
+ * is quantised to qb bits, 0..8, per pair); NaN keys rank as +inf.  dists/ids (nq, k): the k
+ * smallest (key, list_ids[i]) over all probed lists, ascending, ties to the smaller id, padded
+ * with (+inf, 0xFFFFFFFF); INNER_PRODUCT keys are the negated estimates.  k in [1, 256],
+ * nlist <= 16383.  Stream-ordered, no host synchronisation; the workspace size depends on the
+ * shape alone (queries are processed in chunks; at most 1 GiB) and is 0 for invalid sizes. */
+size_t mivq_ivf_rabitq_search_workspace_bytes(int64_t nq, int64_t n, int32_t nlist,
+                                              int32_t nprobe, int32_t d, int32_t k);
+int mivq_ivf_rabitq_search(const float* q, int64_t nq, int32_t d, const float* coarse,
+                           int32_t nlist, const uint32_t* probe_l, int32_t nprobe,
+                           const int64_t* offsets, const uint8_t* list_codes,
+                           const uint32_t* list_ids, int32_t qb, int32_t metric, int32_t k,
+                           void* workspace, size_t workspace_bytes, float* dists, uint32_t* ids,
+                           void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

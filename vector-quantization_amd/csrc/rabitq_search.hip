@@ -19,6 +19,7 @@
 // The (nq, m) key blocks go through launch_tiled_topk (segmented top-k + running merge), the
 // same selection as the exact flat search: (key, id) ascending, ties to the smaller id.
 #include "mivq_common.h"
+#include "rabitq_internal.h"
 #include "topk.h"
 
 #include <math.h>
@@ -32,119 +33,19 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));  // code rows are 4-B aligned
 
-constexpr int kQfStride = 8;  // floats per query: c1, c2, c34, qc, qn, 1/sqrt(d), off, 0
-
 __device__ __forceinline__ void lds_fence() {
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
     __builtin_amdgcn_wave_barrier();
 }
 
 // One workgroup (256 threads) per query.  qq: (nq, d) int8 (q' - off), qr: (nq, d) f32 r
-// (qb = 0 only), qf: (nq, kQfStride) f32.
+// (qb = 0 only), qf: (nq, kQfStride) f32.  The body is rabitq_qprep_row (rabitq_internal.h).
 __global__ __launch_bounds__(256) void rabitq_qprep_kernel(const float* __restrict__ q, int d,
                                                            const float* __restrict__ centroid, int qb,
                                                            int8_t* __restrict__ qq, float* __restrict__ qr,
                                                            float* __restrict__ qf) {
-    __shared__ float red_lo[256], red_hi[256];
-    __shared__ int red_sum;
-    const int tid = threadIdx.x;
     const int64_t a = blockIdx.x;
-    const float* qrow = q + a * d;
-    float lo = INFINITY, hi = -INFINITY;
-    for (int j = tid; j < d; j += 256) {
-        const float r = __fsub_rn(qrow[j], centroid ? centroid[j] : 0.0f);
-        lo = fminf(lo, r);
-        hi = fmaxf(hi, r);
-        if (qb == 0) qr[a * d + j] = r;
-    }
-    red_lo[tid] = lo;
-    red_hi[tid] = hi;
-    if (tid == 0) red_sum = 0;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-            red_lo[tid] = fminf(red_lo[tid], red_lo[tid + s]);
-            red_hi[tid] = fmaxf(red_hi[tid], red_hi[tid + s]);
-        }
-        __syncthreads();
-    }
-    const float vmin = red_lo[0], vmax = red_hi[0];
-    const float isd = __fdiv_rn(1.0f, sqrtf((float)d));
-    float delta = 0.0f;
-    const int off = qb == 8 ? 128 : 0;
-    if (qb > 0) {
-        const int top = (1 << qb) - 1;
-        delta = __fdiv_rn(__fsub_rn(vmax, vmin), (float)top);
-        const float inv_delta = delta > 0.0f ? __fdiv_rn(1.0f, delta) : 0.0f;
-        int part = 0;
-        for (int j = tid; j < d; j += 256) {
-            const float r = __fsub_rn(qrow[j], centroid ? centroid[j] : 0.0f);
-            const float t = __fmul_rn(__fsub_rn(r, vmin), inv_delta);
-            int v = (int)floorf(__fadd_rn(t, 0.5f));
-            v = v < 0 ? 0 : (v > top ? top : v);
-            part += v;
-            qq[a * d + j] = (int8_t)(v - off);
-        }
-        atomicAdd(&red_sum, part);  // integer: order-free
-    }
-    __syncthreads();
-    if (tid < 64) {
-        // the oracle's sequential chains, both in lane 0, over the row staged in LDS 1024
-        // elements at a time by the whole wave: the global loads of a piece are in flight at
-        // once instead of one round trip per element of a serial loop
-        __shared__ __attribute__((aligned(16))) float s_q[1024], s_c[1024];
-        float qc = 0.0f, qn = 0.0f;
-        for (int j0 = 0; j0 < d; j0 += 1024) {
-            const int nj = min(1024, d - j0);
-            for (int t = tid; t < nj; t += 64) {
-                s_q[t] = qrow[j0 + t];
-                s_c[t] = centroid ? centroid[j0 + t] : 0.0f;
-            }
-            __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's own LDS stores
-            __builtin_amdgcn_wave_barrier();
-            if (tid == 0) {  // both chains in lane 0, 16-B LDS reads running ahead of the fmas
-                int t = 0;
-#pragma unroll 4
-                for (; t + 4 <= nj; t += 4) {
-                    const float4 qv = *reinterpret_cast<const float4*>(s_q + t);
-                    const float4 cv = *reinterpret_cast<const float4*>(s_c + t);
-                    float r = __fsub_rn(qv.x, cv.x); qc = __builtin_fmaf(r, r, qc); qn = __builtin_fmaf(qv.x, qv.x, qn);
-                    r = __fsub_rn(qv.y, cv.y); qc = __builtin_fmaf(r, r, qc); qn = __builtin_fmaf(qv.y, qv.y, qn);
-                    r = __fsub_rn(qv.z, cv.z); qc = __builtin_fmaf(r, r, qc); qn = __builtin_fmaf(qv.z, qv.z, qn);
-                    r = __fsub_rn(qv.w, cv.w); qc = __builtin_fmaf(r, r, qc); qn = __builtin_fmaf(qv.w, qv.w, qn);
-                }
-                for (; t < nj; ++t) {
-                    const float r = __fsub_rn(s_q[t], s_c[t]);
-                    qc = __builtin_fmaf(r, r, qc);
-                    qn = __builtin_fmaf(s_q[t], s_q[t], qn);
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-        float c1 = 0.0f, c2 = 0.0f, c34 = 0.0f;
-        if (qb > 0) {
-            c1 = __fmul_rn(__fmul_rn(2.0f, delta), isd);
-            c2 = __fmul_rn(__fmul_rn(2.0f, vmin), isd);
-            c34 = __fmul_rn(isd, __fadd_rn(__fmul_rn(delta, (float)red_sum), __fmul_rn((float)d, vmin)));
-        }
-        if (tid == 0) {
-            float* f = qf + a * kQfStride;
-            f[0] = c1; f[1] = c2; f[2] = c34; f[3] = qc; f[4] = qn; f[5] = isd; f[6] = (float)off; f[7] = 0.0f;
-        }
-    }
-}
-
-// The estimator epilogue shared by both kernels (oracle order).
-__device__ __forceinline__ float rabitq_key(float fd, float f0, float f1, float qc, float qn, bool ip) {
-    const float pre = __builtin_fmaf(__fmul_rn(-2.0f, f1), fd, __fadd_rn(f0, qc));
-    return ip ? __fmul_rn(0.5f, __fsub_rn(pre, qn)) : pre;
-}
-
-__device__ __forceinline__ float load_f32(const unsigned char* p) {
-    uint32_t u = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) u |= (uint32_t)p[b] << (8 * b);
-    return __uint_as_float(u);
+    rabitq_qprep_row(q + a * d, d, centroid, qb, qq + a * d, qr + a * d, qf + a * kQfStride);
 }
 
 constexpr int kEstWaves = 8;  // waves per workgroup (all share the query block in LDS)
@@ -223,9 +124,7 @@ __global__ __launch_bounds__(kEstWaves * 64) void rabitq_est_mfma_kernel(
         auto kstep = [&](uint32_t dw, int s) __attribute__((always_inline)) {
             const uint32_t b16 = (dw >> sh) & 0xFFFFu;
             pc += __builtin_popcount(b16);
-            v4i av;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) av[j] = (int)(__umul24((b16 >> (4 * j)) & 0xFu, 0x204081u) & 0x01010101u);
+            const v4i av = rabitq_sign_bytes(b16);
             const v4i bq = *reinterpret_cast<const v4i*>(qrow + 32 * s);
             acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bq, acc, 0, 0, 0);
         };
@@ -448,9 +347,7 @@ __global__ __launch_bounds__(kEstWaves * 64) void rabitq_est_mq_kernel(
                     __builtin_amdgcn_sched_barrier(0);
                     const uint32_t b16 = (cg[gg][u] >> sh) & 0xFFFFu;
                     pc += __builtin_popcount(b16);
-                    v4i av;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) av[j] = (int)(__umul24((b16 >> (4 * j)) & 0xFu, 0x204081u) & 0x01010101u);
+                    const v4i av = rabitq_sign_bytes(b16);
 #pragma unroll
                     for (int jb = 0; jb < NQB; ++jb) acc[jb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bq[jb], acc[jb], 0, 0, 0);
 #pragma unroll

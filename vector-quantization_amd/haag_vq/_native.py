@@ -103,6 +103,10 @@ SIGNATURES = {
     "mivq_ivfpq_search_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "mivq_ivfpq_search": (_c.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32,
                                      _vp, _sz, _vp, _vp, _vp]),
+    "mivq_ivf_rabitq_encode": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp]),
+    "mivq_ivf_rabitq_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32, _i32]),
+    "mivq_ivf_rabitq_search": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32,
+                                          _vp, _sz, _vp, _vp, _vp]),
 }
 
 ABI_VERSION = 2  # MIVQ_ABI_VERSION of include/mivq.h the table above binds
@@ -818,3 +822,51 @@ def ivfpq_search(lut: torch.Tensor, probe_d: torch.Tensor, probe_l: torch.Tensor
           _stream())
     return dists, ids
 
+
+
+def ivf_rabitq_encode(x: torch.Tensor, coarse: torch.Tensor, assign: torch.Tensor, metric: int,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """RaBitQ-1 code rows whose centre is the row's list centroid coarse[assign[i]]; bit-identical
+    to rabitq_encode(row, coarse[assign[i]], metric).  assign values >= nlist are undefined."""
+    _check(x, "x", torch.float32, 2)
+    _check(coarse, "coarse", torch.float32, 2)
+    _check(assign, "assign", torch.int32, 1)
+    n, d = x.shape
+    if coarse.shape[1] != d or assign.shape[0] != n:
+        raise ValueError("ivf_rabitq_encode: shape mismatch")
+    if out is None:
+        out = torch.empty((n, rabitq_code_size(d)), dtype=torch.uint8, device=x.device)
+    else:
+        _check(out, "out", torch.uint8, 2)
+        if tuple(out.shape) != (n, rabitq_code_size(d)):
+            raise ValueError("ivf_rabitq_encode: out has the wrong shape")
+    _call("mivq_ivf_rabitq_encode", _ptr(x), n, d, _ptr(coarse), coarse.shape[0], _ptr(assign), metric, _ptr(out),
+          _stream())
+    return out
+
+
+def ivf_rabitq_search(q: torch.Tensor, coarse: torch.Tensor, probe_l: torch.Tensor, offsets: torch.Tensor,
+                      list_codes: torch.Tensor, list_ids: torch.Tensor, qb: int, metric: int,
+                      k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """RaBitQ estimator search over the probed lists: (keys f32 (nq, k), ids int32 (nq, k) holding
+    uint32 ids), ascending; IP keys are negated estimates; missing slots hold (+inf, 0xFFFFFFFF)."""
+    _check(q, "q", torch.float32, 2)
+    _check(coarse, "coarse", torch.float32, 2)
+    _check(probe_l, "probe_l", torch.int32, 2)
+    _check(offsets, "offsets", torch.int64, 1)
+    _check(list_codes, "list_codes", torch.uint8, 2)
+    _check(list_ids, "list_ids", torch.int32, 1)
+    nq, d = q.shape
+    nlist, nprobe = coarse.shape[0], probe_l.shape[1]
+    n = list_codes.shape[0]
+    if coarse.shape[1] != d or list_codes.shape[1] != rabitq_code_size(d):
+        raise ValueError(f"ivf_rabitq_search: code rows {list_codes.shape[1]} B / coarse d={coarse.shape[1]} do not "
+                         f"match d={d}")
+    if probe_l.shape[0] != nq or offsets.shape[0] != nlist + 1 or list_ids.shape[0] != n:
+        raise ValueError("ivf_rabitq_search: shape mismatch")
+    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+    ws = workspace(load_library().mivq_ivf_rabitq_search_workspace_bytes(nq, n, nlist, nprobe, d, k), q.device)
+    _call("mivq_ivf_rabitq_search", _ptr(q), nq, d, _ptr(coarse), nlist, _ptr(probe_l), nprobe, _ptr(offsets),
+          _ptr(list_codes), _ptr(list_ids), qb, metric, k, _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids), _stream())
+    return dists, ids

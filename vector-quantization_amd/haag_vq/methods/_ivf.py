@@ -15,6 +15,9 @@ of benchmarks/ivf_benchmark.py:170-204:
   precomputed table into one number per code, so a query needs only its own M x ksub LUT:
       ||q - c_l - r_i||^2 = ||q - c_l||^2 + tau_i - 2 q.r_i,  tau_i = ||r_i||^2 + 2 c_l.r_i.
   IP (IndexFlatIP quantizer): score = q.c_l + q.r_i, ranked as its negation.
+* ``IvfRaBitQ``  RaBitQ-1 codes of x - coarse[list(x)] (faiss ``IVF{nlist},RaBitQ``): the encode
+  whose centre is the row's list centroid, lists in bucket order, and the estimator search over
+  the probed lists with the query residual re-quantised per (query, list) pair.
 
 faiss itself is absent here, so coarse centroids, codebooks and results are not claimed to
 equal faiss'; the arithmetic is the canonical one of include/mivq.h and oracle/.
@@ -116,7 +119,7 @@ def train_coarse(X: torch.Tensor, K: int, niter: int = 10, seed: int = 1234, max
 class IvfLists:
     """Inverted lists in bucket order (device tensors)."""
     offsets: torch.Tensor     # (K+1,) int64
-    codes: torch.Tensor       # (N, M) uint8, one byte per sub-code
+    codes: torch.Tensor       # (N, M) uint8, one byte per sub-code (IvfRaBitQ: RaBitQ-1 code rows)
     ids: torch.Tensor         # (N,) int32 holding uint32 ids
     tau: Optional[torch.Tensor]  # (N,) f32, L2 only
 
@@ -197,3 +200,58 @@ class IvfPq:
         lut = _native.adc_lut(Q, self.pq, self.nbits, _native.METRIC_INNER_PRODUCT)
         L = self.lists
         return _native.ivfpq_search(lut, pd, pl, L.offsets, L.codes, L.ids, L.tau, self.metric, k, self.nbits)
+
+
+class IvfRaBitQ:
+    """IVF over RaBitQ-1 codes (device-resident); the engine behind RaBitQIVFIndex."""
+
+    def __init__(self, d: int, K: int, metric: int = _native.METRIC_L2) -> None:
+        self.d, self.K, self.metric = d, K, metric
+        self.coarse: Optional[torch.Tensor] = None
+        self.lists: Optional[IvfLists] = None
+        self.ntotal = 0
+
+    def train(self, X: torch.Tensor, coarse_iters: int = 10, seed: int = 1234) -> None:
+        self.coarse = train_coarse(X, self.K, niter=coarse_iters, seed=seed, metric=self.metric)
+
+    def _encode(self, X: torch.Tensor):
+        n = X.shape[0]
+        a = torch.empty(n, dtype=torch.int32, device=X.device)
+        codes = torch.empty((n, _native.rabitq_code_size(self.d)), dtype=torch.uint8, device=X.device)
+        step = _rows_per_chunk(self.K)
+        for s in range(0, n, step):
+            e = min(n, s + step)
+            _, a[s:e] = assign(X[s:e], self.coarse, self.metric)
+            _native.ivf_rabitq_encode(X[s:e], self.coarse, a[s:e], self.metric, out=codes[s:e])
+        return a, codes
+
+    def add(self, X: torch.Tensor) -> None:
+        """Append rows (ids continue from ntotal); lists are rebuilt in bucket order."""
+        a, codes = self._encode(X)
+        ids = torch.arange(self.ntotal, self.ntotal + X.shape[0], dtype=torch.int64, device=X.device).to(torch.int32)
+        if self.lists is not None and self.ntotal > 0:
+            old = self.lists
+            # recover the row-order arrays of the existing lists from their bucket order
+            a_old = torch.repeat_interleave(torch.arange(self.K, dtype=torch.int32, device=X.device),
+                                            (old.offsets[1:] - old.offsets[:-1]))
+            a = torch.cat([a_old, a])
+            codes = torch.cat([old.codes, codes])
+            ids = torch.cat([old.ids, ids])
+        offsets, order = _native.bucket_sort(a.contiguous(), self.K)
+        self.lists = IvfLists(
+            offsets=offsets,
+            codes=(_native.gather_rows(codes.contiguous(), order) if codes.shape[1] % 4 == 0
+                   else codes[order.long()].contiguous()),
+            ids=_native.gather_rows(ids.contiguous(), order),
+            tau=None,
+        )
+        self.ntotal += X.shape[0]
+
+    def search(self, Q: torch.Tensor, k: int, nprobe: int, qb: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(keys f32 (nq, k), ids int32 (nq, k)); L2 estimates ascending, IP as negated estimates."""
+        nprobe = max(1, min(int(nprobe), self.K))
+        if nprobe > 256:
+            raise ValueError(f"nprobe={nprobe}: the probe selection (mivq_topk_rows) supports at most 256 lists")
+        _, pl = _native.topk_rows(_native.pairwise_distances(Q, self.coarse, self.metric), nprobe)
+        L = self.lists
+        return _native.ivf_rabitq_search(Q, self.coarse, pl, L.offsets, L.codes, L.ids, qb, self.metric, k)

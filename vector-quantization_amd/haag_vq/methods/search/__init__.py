@@ -1,5 +1,6 @@
 from .faiss_ivfpq_index import FaissIvfPqIndex
 from .flat_quantized_index import FlatQuantizedIndex, FlatADCIndex, search_codes
 from .rabitq_index import RaBitQIndex
+from .rabitq_ivf_index import RaBitQIVFIndex
 
-__all__ = ["FaissIvfPqIndex", "FlatQuantizedIndex", "FlatADCIndex", "RaBitQIndex", "search_codes"]
+__all__ = ["FaissIvfPqIndex", "FlatQuantizedIndex", "FlatADCIndex", "RaBitQIndex", "RaBitQIVFIndex", "search_codes"]
