@@ -155,6 +155,30 @@ def test_search_workspace_sizes_pinned():
         for shape, want in table.items():
             assert fn(*shape) == want, (fn.__name__, shape, fn(*shape), want)
 
+    # The four exact searches (f32, SQ, RaBitQ-1, LVQ codes), read from the library while the f32
+    # search still had a scan and a layout of its own.  Both sides of the tiled threshold
+    # (nq 15 / 16, n 4095 / 4096); the last d and the first d past each queries-per-workgroup step
+    # (8, 4, 2, 1, none) of the format's LDS policy, at 15 queries so that the step changes the
+    # number of query blocks (f32: 96 KiB of queries; the code formats: 128 KiB of queries plus
+    # two (SQ) or one parameter rows; 160 KiB at one query); 1, 2 and 3 queries, where the code
+    # formats narrow the query block to the batch; no streaming scan past the last step.
+    either_side = {(15, 4095, 1536, 10): 76800, (15, 4096, 1536, 10): 76800, (16, 4095, 1536, 10): 81920,
+                   (16, 4096, 1536, 10): 266240}
+    small_batch = {(1, 1_000_000, 3072, 100): 3136000, (2, 1_000_000, 3072, 100): 6272000,
+                   (3, 1_000_000, 3072, 100): 9408000}
+    by_step = (2361856, 1190400, 1190400, 614400, 614400, 326656, 326656, 0)
+    steps = (
+        (lib.mivq_flat_search_workspace_bytes, (3072, 3076, 6144, 6148, 12288, 12292, 40960, 40964)),
+        (lib.mivq_sq_flat_search_workspace_bytes, (3276, 3280, 5460, 5464, 8192, 8196, 13652, 13656)),
+        (lib.mivq_rabitq_flat_search_workspace_bytes, (3640, 3644, 6552, 6556, 10920, 10924, 20480, 20484)),
+        (lib.mivq_lvq_flat_search_workspace_bytes, (3640, 3644, 6552, 6556, 10920, 10924, 20480, 20484)),
+    )
+    for fn, ds in steps:
+        table = {**either_side, **small_batch, **{(15, 1_000_000, d, 10): want for d, want in zip(ds, by_step)},
+                 (1, 5000, ds[-1], 256): 0, (16, 4096, ds[-1], 10): 266240}
+        for shape, want in table.items():
+            assert fn(*shape) == want, (fn.__name__, shape, fn(*shape), want)
+
 
 def test_qscan_valu_counts_match_bench():
     """bench.py prices the filtered ADC scan's roofline from the static VALU count of one

@@ -29,16 +29,23 @@ def _clustered(rng, n, d, centers=16, spread=0.3):
     return X.astype(np.float32)
 
 
-@pytest.mark.parametrize("n,m,d", [(300, 70, 32), (129, 65, 1536), (5, 3, 7), (1000, 256, 96), (64, 4096, 16)])
+@pytest.mark.parametrize("n,m,d,y_off", [
+    pytest.param(*s, 0, id="-".join(map(str, s)))
+    for s in [(300, 70, 32), (129, 65, 1536), (5, 3, 7), (1000, 256, 96), (64, 4096, 16)]
+] + [pytest.param(129, 65, 64, 1, id="129-65-64-y_one_float_in")])  # y off 16 B: scalar fetches
 @pytest.mark.parametrize("metric", [1, 0])
-def test_pairwise_distances_bit_exact(dev, oracle, n, m, d, metric):
+def test_pairwise_distances_bit_exact(dev, oracle, n, m, d, y_off, metric):
     from haag_vq import _native
 
     rng = np.random.default_rng(n + m + d)
     X = rng.standard_normal((n, d)).astype(np.float32)
     Y = rng.standard_normal((m, d)).astype(np.float32)
     Y[1] = X[0]  # an exact zero distance
-    got = _h(_native.pairwise_distances(_t(X, dev), _t(Y, dev), metric))
+    buf = torch.zeros(m * d + y_off, dtype=torch.float32, device=dev)
+    buf[y_off:] = _t(Y.reshape(-1), dev)
+    Yd = buf[y_off:].view(m, d)
+    assert (Yd.data_ptr() % 16 != 0) == bool(y_off)
+    got = _h(_native.pairwise_distances(_t(X, dev), Yd, metric))
     np.testing.assert_array_equal(got, oracle.pairwise(X, Y, metric))
 
 

@@ -449,7 +449,10 @@ def test_adc_lut_misaligned_centroids(dev, oracle, offset):
 
 @pytest.mark.parametrize("nq,n,d,k", [
     (20, 3000, 1024, 10), (7, 500, 37, 100), (4, 3, 16, 5),    # streaming scan
-    (100, 20000, 96, 10),                                         # tiled, one chunk, 5 segments
+    (3, 200, 3076, 5), (3, 200, 6148, 5), (2, 100, 12292, 3),    # 4, 2 and 1 queries per workgroup
+    (9, 700, 64, 65), (9, 700, 64, 129), (9, 700, 64, 200),      # 2, 3 and 4 list registers, streaming
+    (5, 300, 4, 1),                                               # smallest d and k
+    (100, 20000, 96, 10),                                        # tiled, one chunk, 5 segments
     (4100, 40000, 16, 10),                                        # tiled, 3 chunks + running merge
     (64, 5000, 30, 100),                                          # tiled, d % 4 != 0
     (16, 4096, 1536, 256),                                        # tiled, k = 256
@@ -466,6 +469,28 @@ def test_flat_search_bit_exact(dev, oracle, nq, n, d, k, metric):
         X[n // 2] = X[3]
     d_ref, i_ref = oracle.flat_search(Q, X, k, metric)
     dd, ii = _native.flat_search(_t(Q, dev), _t(X, dev), k, metric)
+    np.testing.assert_array_equal(_h(dd), d_ref)
+    np.testing.assert_array_equal(_h(ii).view(np.uint32), i_ref)
+
+
+@pytest.mark.parametrize("nq,n", [(3, 1000), (16, 4100)])  # streaming scan, tiled
+@pytest.mark.parametrize("metric", [1, 0])
+def test_flat_search_misaligned_database(dev, oracle, nq, n, metric):
+    """A database that starts one float into its buffer (d % 4 == 0, rows 4-B aligned only): the
+    scan reads its rows element by element and the tile fetches y scalar by scalar, same results."""
+    from haag_vq import _native
+
+    d, k = 64, 10
+    rng = np.random.default_rng(n)
+    X = rng.standard_normal((n, d)).astype(np.float32)
+    Q = rng.standard_normal((nq, d)).astype(np.float32)
+    X[n - 1] = X[3]
+    buf = torch.zeros(n * d + 1, dtype=torch.float32, device=dev)
+    buf[1:] = _t(X.reshape(-1), dev)
+    Xv = buf[1:].view(n, d)
+    assert Xv.data_ptr() % 16 != 0
+    d_ref, i_ref = oracle.flat_search(Q, X, k, metric)
+    dd, ii = _native.flat_search(_t(Q, dev), Xv, k, metric)
     np.testing.assert_array_equal(_h(dd), d_ref)
     np.testing.assert_array_equal(_h(ii).view(np.uint32), i_ref)
 

@@ -1,12 +1,20 @@
-"""Interleaved A/B of mivq_pq_encode between two builds of libmivq.so (same process, same data).
+"""Interleaved A/B of one entry point between two builds of libmivq.so (same process, same data).
 
-usage: python tools/ab_lib.py OTHER.so [--what encode|adc|lut] [--n 1000000] [--d 1536] [--M 16]
-                              [--data gaussian] [--reps 10] [--nq 1000] [--k 10]
+usage: python tools/ab_lib.py OTHER.so [--what encode|adc|lut|flat|sq|rabitq|lvq|pairwise]
+                              [--n 1000000] [--d 1536] [--M 16] [--data gaussian] [--reps 10]
+                              [--nq 1000] [--k 10] [--metric l2|ip] [--nbits 8] [--this THIS.so]
 The in-tree library (vector-quantization_amd/lib/libmivq.so) is "this"; OTHER.so is e.g. a
 build of the previous commit (git stash; make; cp lib/libmivq.so /tmp/old.so; git stash pop).
+--this names another build in its place (the same file as OTHER.so: an A/A pass, the noise floor
+of the comparison).  Both must report this build's mivq_abi_version().
 Prints per-call medians of alternating single calls (HIP events) and back-to-back rates, and
-checks that both builds emit identical codes (--what adc: mivq_adc_search over the encoded
-rows, identical ids and distances).
+checks that both builds give identical outputs:
+  encode    mivq_pq_encode, the codes
+  adc, lut  mivq_adc_search over the encoded rows (ids and distances), mivq_adc_lut
+  flat, sq, rabitq, lvq   the exact searches mivq_flat_search, mivq_sq_flat_search,
+            mivq_rabitq_flat_search, mivq_lvq_flat_search (SQ / LVQ: --nbits) of --nq queries
+            over seeded random rows / codes, ids and distances
+  pairwise  mivq_pairwise_distances of --n rows against --nq rows, the whole matrix
 """
 import argparse
 import ctypes
@@ -22,6 +30,8 @@ from haag_vq import _native  # noqa: E402
 from haag_vq.methods._kmeans import train_pq  # noqa: E402
 from bench import synth  # noqa: E402
 
+P = ctypes.c_void_p
+
 
 def bind(path):
     lib = ctypes.CDLL(str(path))
@@ -29,27 +39,91 @@ def bind(path):
         if hasattr(lib, name):
             f = getattr(lib, name)
             f.restype, f.argtypes = res, args
+    want = _native.load_library().mivq_abi_version()
+    got = lib.mivq_abi_version() if hasattr(lib, "mivq_abi_version") else None
+    if got != want:  # SIGNATURES describes this build's ABI only
+        sys.exit(f"ab_lib: {path} has ABI version {got}, this build {want}")
     return lib
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("other")
-    ap.add_argument("--n", type=int, default=1_000_000)
-    ap.add_argument("--d", type=int, default=1536)
-    ap.add_argument("--M", type=int, default=16)
-    ap.add_argument("--data", default="gaussian")
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--what", choices=("encode", "adc", "lut"), default="encode")
-    ap.add_argument("--nq", type=int, default=1000)
-    ap.add_argument("--k", type=int, default=10)
-    a = ap.parse_args()
-    dev = _native.require_device()
-    libs = {"this": bind(_native.LIB_PATH), "other": bind(a.other if Path(a.other).is_absolute() else ROOT / a.other)}
+def _ptr(t):
+    return None if t is None else P(t.data_ptr())
+
+
+def _rows(n, code_bytes, trailer, seed, dev):
+    """(n, code_bytes + 8 * trailer) random code bytes; the trailer two floats in [0.5, 1.5)."""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    rows = torch.randint(0, 256, (n, code_bytes + 8 * trailer), dtype=torch.uint8, device=dev, generator=g)
+    if trailer:
+        f = torch.rand((n, 2), dtype=torch.float32, device=dev, generator=g) + 0.5
+        rows[:, code_bytes:] = f.view(torch.uint8)
+    return rows
+
+
+# --what of an exact search: its entry point and, from (args, device), the database and the
+# arguments that stand between d and the metric in its signature.
+def _f32_db(a, dev):
+    return synth(a.n, a.d, 0, dev, kind=a.data), []
+
+
+def _sq_db(a, dev):
+    lo = synth(1, a.d, 3, dev).reshape(-1)
+    den = lo.abs() + 0.5
+    return _rows(a.n, {4: (a.d + 1) // 2, 8: a.d, 16: 2 * a.d}[a.nbits], 0, 5, dev), [lo, den, a.nbits]
+
+
+def _rabitq_db(a, dev):
+    return _rows(a.n, (a.d + 7) // 8, 1, 5, dev), [synth(1, a.d, 3, dev).reshape(-1)]
+
+
+def _lvq_db(a, dev):
+    return _rows(a.n, (a.d * a.nbits + 7) // 8, 1, 5, dev), [synth(1, a.d, 3, dev).reshape(-1), a.nbits]
+
+
+EXACT = {
+    "flat": ("mivq_flat_search", _f32_db),
+    "sq": ("mivq_sq_flat_search", _sq_db),
+    "rabitq": ("mivq_rabitq_flat_search", _rabitq_db),
+    "lvq": ("mivq_lvq_flat_search", _lvq_db),
+}
+
+
+def exact_leg(a, libs, dev, st):
+    """run(k) and outputs() of an exact search or of mivq_pairwise_distances."""
+    metric = _native.METRIC_L2 if a.metric == "l2" else _native.METRIC_INNER_PRODUCT
+    Q = synth(a.nq, a.d, 7, dev, kind=a.data)
+    if a.what == "pairwise":
+        X = synth(a.n, a.d, 0, dev, kind=a.data)
+        out = {k: torch.empty((a.n, a.nq), dtype=torch.float32, device=dev) for k in libs}
+
+        def run(k):
+            rc = libs[k].mivq_pairwise_distances(_ptr(X), a.n, _ptr(Q), a.nq, a.d, metric, _ptr(out[k]), P(st))
+            assert rc == 0, (rc, libs[k].mivq_last_error())
+
+        return run, lambda k: (out[k],)
+    name, make = EXACT[a.what]
+    db, params = make(a, dev)
+    bufs = {}
+    for k, lb in libs.items():
+        nb = getattr(lb, name + "_workspace_bytes")(a.nq, a.n, a.d, a.k)
+        bufs[k] = (torch.empty(max(nb, 256), dtype=torch.uint8, device=dev),
+                   torch.empty((a.nq, a.k), dtype=torch.float32, device=dev),
+                   torch.empty((a.nq, a.k), dtype=torch.int32, device=dev))
+
+    def run(k):
+        ws, od, oi = bufs[k]
+        mid = [_ptr(v) if isinstance(v, torch.Tensor) else v for v in params]
+        rc = getattr(libs[k], name)(_ptr(Q), a.nq, _ptr(db), a.n, a.d, *mid, metric, a.k, 0, _ptr(ws), ws.numel(),
+                                    _ptr(od), _ptr(oi), P(st))
+        assert rc == 0, (rc, libs[k].mivq_last_error())
+
+    return run, lambda k: bufs[k][1:]
+
+
+def pq_leg(a, libs, dev, st):
+    """run(k) and outputs() of mivq_pq_encode, mivq_adc_lut or mivq_adc_search."""
     X = synth(a.n, a.d, 0, dev, kind=a.data)
     C = train_pq(X[:65536], a.M, 8, niter=25, seed=1234).contiguous()
-    st = torch.cuda.current_stream().cuda_stream
-    P = ctypes.c_void_p
     state = {}
     for k, lb in libs.items():
         prep = torch.empty(lb.mivq_pq_prep_bytes(a.d, a.M, 8), dtype=torch.uint8, device=dev)
@@ -66,48 +140,61 @@ def main():
                                P(ws.data_ptr()), ws.numel(), P(out.data_ptr()), 0, P(st))
         assert rc == 0, rc
 
-    run = run_encode
-    for k in libs:
-        run_encode(k)
-    torch.cuda.synchronize()
-    same = bool(torch.equal(state["this"][2], state["other"][2]))
-    if a.what == "lut":  # mivq_adc_lut alone: the LUTs of nq queries, compared bit for bit
-        Q = synth(a.nq, a.d, 7, dev, kind=a.data)
+    if a.what == "encode":
+        return run_encode, lambda k: (state[k][2],)
+    Q = synth(a.nq, a.d, 7, dev, kind=a.data)
+    if a.what == "lut":  # mivq_adc_lut alone: the LUTs of nq queries
         luts = {k: torch.empty((a.nq, a.M, 256), dtype=torch.float32, device=dev) for k in libs}
 
         def run_lut(k):
             rc = libs[k].mivq_adc_lut(P(Q.data_ptr()), a.nq, a.d, a.M, 8, P(C.data_ptr()), 1, P(luts[k].data_ptr()), P(st))
             assert rc == 0, rc
 
-        run = run_lut
-        for k in libs:
-            run_lut(k)
-        torch.cuda.synchronize()
-        same = bool(torch.equal(luts["this"], luts["other"]))
-    if a.what == "adc":
-        codes = state["this"][2]
-        Q = synth(a.nq, a.d, 7, dev, kind=a.data)
-        lut = torch.empty((a.nq, a.M, 256), dtype=torch.float32, device=dev)
-        assert libs["this"].mivq_adc_lut(P(Q.data_ptr()), a.nq, a.d, a.M, 8, P(C.data_ptr()), 1, P(lut.data_ptr()),
-                                         P(st)) == 0
-        adc = {}
-        for k, lb in libs.items():
-            nb = lb.mivq_adc_search_workspace_bytes(a.nq, a.n, a.M, 8, a.k)
-            adc[k] = (torch.empty(max(nb, 256), dtype=torch.uint8, device=dev),
-                      torch.empty((a.nq, a.k), dtype=torch.float32, device=dev),
-                      torch.empty((a.nq, a.k), dtype=torch.int32, device=dev))
+        return run_lut, lambda k: (luts[k],)
+    run_encode("this")
+    codes = state["this"][2]
+    lut = torch.empty((a.nq, a.M, 256), dtype=torch.float32, device=dev)
+    assert libs["this"].mivq_adc_lut(P(Q.data_ptr()), a.nq, a.d, a.M, 8, P(C.data_ptr()), 1, P(lut.data_ptr()),
+                                     P(st)) == 0
+    adc = {}
+    for k, lb in libs.items():
+        nb = lb.mivq_adc_search_workspace_bytes(a.nq, a.n, a.M, 8, a.k)
+        adc[k] = (torch.empty(max(nb, 256), dtype=torch.uint8, device=dev),
+                  torch.empty((a.nq, a.k), dtype=torch.float32, device=dev),
+                  torch.empty((a.nq, a.k), dtype=torch.int32, device=dev))
 
-        def run_adc(k):
-            ws, od, oi = adc[k]
-            rc = libs[k].mivq_adc_search(P(lut.data_ptr()), a.nq, P(codes.data_ptr()), a.n, a.M, 8, a.k, 0,
-                                         P(ws.data_ptr()), ws.numel(), P(od.data_ptr()), P(oi.data_ptr()), 0, P(st))
-            assert rc == 0, rc
+    def run_adc(k):
+        ws, od, oi = adc[k]
+        rc = libs[k].mivq_adc_search(P(lut.data_ptr()), a.nq, P(codes.data_ptr()), a.n, a.M, 8, a.k, 0,
+                                     P(ws.data_ptr()), ws.numel(), P(od.data_ptr()), P(oi.data_ptr()), 0, P(st))
+        assert rc == 0, rc
 
-        run = run_adc
-        for k in libs:
-            run_adc(k)
-        torch.cuda.synchronize()
-        same = bool(torch.equal(adc["this"][1], adc["other"][1]) and torch.equal(adc["this"][2], adc["other"][2]))
+    return run_adc, lambda k: adc[k][1:]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("other")
+    ap.add_argument("--this", default=str(_native.LIB_PATH))
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--d", type=int, default=1536)
+    ap.add_argument("--M", type=int, default=16)
+    ap.add_argument("--data", default="gaussian")
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--what", choices=("encode", "adc", "lut", "pairwise", *EXACT), default="encode")
+    ap.add_argument("--nq", type=int, default=1000)
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--metric", choices=("l2", "ip"), default="l2")
+    ap.add_argument("--nbits", type=int, default=8)
+    a = ap.parse_args()
+    dev = _native.require_device()
+    libs = {k: bind(p if Path(p).is_absolute() else ROOT / p) for k, p in (("this", a.this), ("other", a.other))}
+    st = torch.cuda.current_stream().cuda_stream
+    run, outputs = (pq_leg if a.what in ("encode", "adc", "lut") else exact_leg)(a, libs, dev, st)
+    for k in libs:
+        run(k)
+    torch.cuda.synchronize()
+    same = all(torch.equal(x, y) for x, y in zip(outputs("this"), outputs("other")))
     print(f"{a.what}: outputs identical: {same}", flush=True)
     res = {k: [] for k in libs}
     for _ in range(a.reps * 3):

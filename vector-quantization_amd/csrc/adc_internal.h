@@ -1,4 +1,4 @@
-// adc_internal.h — what adc.hip, adc_filtered.hip, flat_search.hip and code_search.hip share.
+// adc_internal.h — what adc.hip, adc_filtered.hip and exact_search.hip share.
 #pragma once
 
 #include "mivq_common.h"

@@ -1,25 +1,33 @@
-// code_search.hip — exact flat search over SQ-4/8/16, RaBitQ-1 and LVQ-1..8 codes on gfx950.
+// exact_search.hip — exact brute-force search on gfx950 over an f32 database
+// (mivq_flat_search, mivq_pairwise_distances) and over SQ-4/8/16, RaBitQ-1 and LVQ-1..8 codes.
 //
-// The code-domain siblings of flat_search.hip's two paths: the packed codes are read once and
-// dequantised in registers, so no fp32 copy of the database exists at any point.  Every
-// reconstruction x^_t is the float the decode kernels write (sq.hip sq_decode_kernel,
-// rabitq.hip rabitq_decode_kernel, lvq.hip lvq_decode_kernel; one rounding per step,
-// -ffp-contract=off) and the distances are the chains of mivq_flat_search, so ids and distances
-// are bit-identical to decode + mivq_flat_search.
+// One distance chain, two paths, every row format.  A format (Fmt<>) says how a row's floats
+// are fetched; f32 is the format with no parameters and no dequantisation.  The packed codes
+// are read once and dequantised in registers, so no fp32 copy of a coded database exists at
+// any point.  Every reconstruction x^_t is the float the decode kernels write (sq.hip
+// sq_decode_kernel, rabitq.hip rabitq_decode_kernel, lvq.hip lvq_decode_kernel; one rounding
+// per step, -ffp-contract=off), so a code search's ids and distances are bit-identical to
+// decode + mivq_flat_search.
 //
-//   code_scan_kernel      the flat_scan_kernel shape: QB queries and the per-dimension
-//                         parameters (SQ: den, lo; RaBitQ: centroid; LVQ: mu) in LDS, lane =
-//                         database row, WaveTopK lists merged by launch_topk_merge.  A row is
+//   code_scan_kernel      the streaming scan: grid (nchunks, ceil(nq / QB)); QB queries and the
+//                         per-dimension parameters (SQ: den, lo; RaBitQ: centroid; LVQ: mu;
+//                         f32: none) in LDS, lane = database row, distances as sequential fmaf
+//                         chains over t, WaveTopK lists merged by launch_topk_merge.  A row is
 //                         read with 16-B (RaBitQ, LVQ: 8-B) loads while whole loads fit and the
 //                         rows are that aligned, then 4-B loads, then single code elements (the
 //                         tail, and every row of an unaligned database).  An LVQ row is an
 //                         MSB-first B-bit stream: 32 dimensions are B whole words, read as one
 //                         unit, byte-swapped, the fields that cross a word funnel-shifted.
-//   code_pairwise_kernel  the pairwise_kernel shape (128 x 64 tile, k-slices of 16 in LDS) as
-//                         launch_tiled_topk's TileFn: the database side of a slice is fetched
-//                         as codes and dequantised before it is stashed.
+//   pairwise_kernel       exact (row, column) distances of two f32 matrices: pairwise_tile
+//                         (128 x 64 per 256-thread workgroup, 8 x 4 scalar chains per thread,
+//                         k-slices of 16 staged transposed in LDS, double-buffered, prefetched
+//                         into registers one slice ahead).  mivq_pairwise_distances (the coarse
+//                         quantizer's exhaustive search, the k-means assignment) and, as
+//                         launch_tiled_topk's TileFn, the tiled path of mivq_flat_search.
+//   code_pairwise_kernel  the same tile as the TileFn of the code searches: the database side of
+//                         a slice is fetched as codes and dequantised before it is stashed.
 //
-// The choice between the two is flat_use_tiled(nq, n); both produce the same chains.
+// The choice between the two paths is flat_use_tiled(nq, n); both produce the same chains.
 #include "adc_internal.h"
 #include "topk.h"
 
@@ -28,34 +36,48 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// kLvq + B - 1 is LVQ with B bits per dimension, B = 1 .. 8
-enum : int { kSq4 = 0, kSq8 = 1, kSq16 = 2, kRbq = 3, kLvq = 4 };
+// kLvq + B - 1 is LVQ with B bits per dimension, B = 1 .. 8; kF32 is the database itself
+enum : int { kSq4 = 0, kSq8 = 1, kSq16 = 2, kRbq = 3, kLvq = 4, kF32 = 12 };
 
-// ---------------------------------------------------------------- code formats
+// Queries per scan workgroup: the queries and the `params` parameter rows of dp = d rounded up
+// to 4 floats share the LDS, within `lds_kib` at 8, 4 or 2 queries and 160 KiB at one.
+struct ScanPolicy {
+    int params;
+    int lds_kib;
+    bool narrow;  // no wider than the batch (search_layout)
+};
+
+// ---------------------------------------------------------------- row formats
 template <int FMT>
 struct Fmt {
-    static constexpr bool kIsLvq = FMT >= kLvq;
+    static constexpr bool kIsLvq = FMT >= kLvq && FMT < kLvq + 8;
     static constexpr int kB = kIsLvq ? FMT - kLvq + 1 : 0;  // LVQ bits per dimension
     static constexpr uint32_t kMask = (1u << kB) - 1u;
     // dims per 32-bit word of codes (LVQ: per unit of kB words)
-    static constexpr int kWordDims = FMT == kSq4 ? 8 : FMT == kSq8 ? 4 : FMT == kSq16 ? 2 : 32;
+    static constexpr int kWordDims = FMT == kSq4 ? 8 : FMT == kSq8 ? 4 : FMT == kSq16 ? 2 : FMT == kF32 ? 1 : 32;
     // words per wide load of the scan (16 B; 8 B for RaBitQ and LVQ, whose rows of d % 64 == 0
     // are 8-B aligned: the 8-byte trailer follows a multiple of 8 code bytes)
     static constexpr int kWideWords = FMT == kRbq || kIsLvq ? 2 : 4;
-    // per-dimension parameter arrays: SQ {den, lo}, RaBitQ {centroid}, LVQ {mu}
-    static constexpr int kParams = FMT == kRbq || kIsLvq ? 1 : 2;
+    // per-dimension parameter arrays: SQ {den, lo}, RaBitQ {centroid}, LVQ {mu}, f32 none
+    static constexpr int kParams = FMT == kF32 ? 0 : FMT == kRbq || kIsLvq ? 1 : 2;
+    // The f32 scan keeps the launch policy it had as a kernel of its own: 96 KiB where the code
+    // formats take 128, and a query block that is not narrowed to the batch.  The difference is
+    // inherited, not measured: nobody has timed either format under the other's policy.
+    static constexpr ScanPolicy kPolicy = {kParams, FMT == kF32 ? 96 : 128, FMT != kF32};
     static constexpr float kLevels = FMT == kSq4 ? 15.0f : FMT == kSq8 ? 255.0f : 65535.0f;
     static constexpr float kRcpLevels = 1.0f / kLevels;  // RN(1 / L)
 
     __host__ __device__ static int code_bytes(int d) {
         if (kIsLvq) return (int)(((int64_t)d * kB + 7) / 8);
-        return FMT == kSq4 ? (d + 1) / 2 : FMT == kSq8 ? d : FMT == kSq16 ? 2 * d : (d + 7) / 8;
+        return FMT == kSq4 ? (d + 1) / 2 : FMT == kSq8 ? d : FMT == kSq16 ? 2 * d : FMT == kF32 ? 4 * d : (d + 7) / 8;
     }
     __host__ __device__ static int row_bytes(int d) { return code_bytes(d) + (FMT == kRbq || kIsLvq ? 8 : 0); }
     // byte offset of dimension t (a multiple of kWordDims) in a row
-    __device__ static int byte_of(int t) { return FMT == kSq4 ? t >> 1 : FMT == kSq8 ? t : FMT == kSq16 ? 2 * t : t >> 3; }
+    __device__ static int byte_of(int t) {
+        return FMT == kSq4 ? t >> 1 : FMT == kSq8 ? t : FMT == kSq16 ? 2 * t : FMT == kF32 ? 4 * t : t >> 3;
+    }
 
-    // level (SQ) / sign bit (RaBitQ) of dimension u of the little-endian words w[]
+    // level (SQ) / sign bit (RaBitQ) / float bits (f32) of dimension u of the little-endian words w[]
     template <int NW>
     __device__ __forceinline__ static uint32_t level(const uint32_t (&w)[NW], int u) {
         if (kIsLvq) {  // w[]: the unit's words byte-swapped, field u at bits [u kB, (u + 1) kB) from the top
@@ -63,6 +85,7 @@ struct Fmt {
             if (end <= 32) return (w[wi] >> (32 - end)) & kMask;
             return ((w[wi] << (end - 32)) | (w[wi + 1 < NW ? wi + 1 : wi] >> (64 - end))) & kMask;
         }
+        if (FMT == kF32) return w[u];
         if (FMT == kSq8) return (w[u >> 2] >> (8 * (u & 3))) & 0xFFu;
         if (FMT == kSq16) return (w[u >> 1] >> (16 * (u & 1))) & 0xFFFFu;
         if (FMT == kSq4) {  // even dimension in the high nibble
@@ -78,6 +101,7 @@ struct Fmt {
             const uint32_t v = (uint32_t)cr[fb] << 8 | cr[fb + 1];
             return (v >> (16 - (o & 7) - kB)) & kMask;
         }
+        if (FMT == kF32) return reinterpret_cast<const uint32_t*>(cr)[t];
         if (FMT == kSq8) return cr[t];
         if (FMT == kSq16) return reinterpret_cast<const uint16_t*>(cr)[t];
         if (FMT == kSq4) {
@@ -90,7 +114,9 @@ struct Fmt {
     // the reciprocal sequence of sq.hip's div_rn_rcp (RN(level / L) for every level 0 .. L).
     // RaBitQ: a = c_t (0 without a centroid), p.x the row's fmul(fmul(fmul(0.5, mult), 2), 1/sqrt(d)).
     // LVQ: a = mu_t, p = the row's {lo, delta}: fadd(fadd(lo, fmul(idx, delta)), mu_t).
+    // f32: the word is x_t.
     __device__ __forceinline__ static float dequant(uint32_t lv, float a, float b, float2 p) {
+        if (FMT == kF32) return __uint_as_float(lv);
         if (kIsLvq) return __fadd_rn(__fadd_rn(p.x, __fmul_rn((float)lv, p.y)), a);
         if (FMT == kRbq) return __fadd_rn(lv ? p.x : -p.x, a);
         const float f = (float)lv;
@@ -127,9 +153,9 @@ __device__ __forceinline__ void scan_words(const uint32_t (&w)[NW], int t0, cons
     static_assert(ND % 4 == 0, "whole groups of four dimensions");
 #pragma unroll
     for (int g = 0; g < ND; g += 4) {
-        const float4 a4 = *reinterpret_cast<const float4*>(pa + t0 + g);
-        float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (Fmt<FMT>::kParams == 2) b4 = *reinterpret_cast<const float4*>(pb + t0 + g);
+        float4 a4 = make_float4(0.f, 0.f, 0.f, 0.f), b4 = a4;
+        if constexpr (Fmt<FMT>::kParams >= 1) a4 = *reinterpret_cast<const float4*>(pa + t0 + g);
+        if constexpr (Fmt<FMT>::kParams == 2) b4 = *reinterpret_cast<const float4*>(pb + t0 + g);
         const float x0 = Fmt<FMT>::dequant(Fmt<FMT>::level(w, g + 0), a4.x, b4.x, p);
         const float x1 = Fmt<FMT>::dequant(Fmt<FMT>::level(w, g + 1), a4.y, b4.y, p);
         const float x2 = Fmt<FMT>::dequant(Fmt<FMT>::level(w, g + 2), a4.z, b4.z, p);
@@ -164,16 +190,18 @@ __global__ __launch_bounds__(kScanWaves * 64) void code_scan_kernel(
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int dp = (d + 3) & ~3;
     float* qv = smem;             // [QB][dp]
-    float* pa = smem + QB * dp;   // SQ den / RaBitQ centroid
+    float* pa = smem + QB * dp;   // SQ den / RaBitQ centroid / LVQ mu
     float* pb = pa + dp;          // SQ lo
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int64_t q0 = (int64_t)blockIdx.y * QB;
     const int nqb = (int)min<int64_t>(QB, nq - q0);
     for (int qq = 0; qq < nqb; ++qq)
         for (int t = tid; t < d; t += kScanWaves * 64) qv[qq * dp + t] = q[(q0 + qq) * d + t];
-    for (int t = tid; t < d; t += kScanWaves * 64) {
-        pa[t] = ga ? ga[t] : 0.0f;
-        if (F::kParams == 2) pb[t] = gb[t];
+    if constexpr (F::kParams >= 1) {
+        for (int t = tid; t < d; t += kScanWaves * 64) {
+            pa[t] = ga ? ga[t] : 0.0f;
+            if (F::kParams == 2) pb[t] = gb[t];
+        }
     }
     __syncthreads();
     WaveTopK<R> top[QB];
@@ -246,7 +274,7 @@ __global__ __launch_bounds__(kScanWaves * 64) void code_scan_kernel(
                 }
             }
             for (; t < d; ++t) {
-                const float xh = F::dequant(F::level_at(cr, t), pa[t], F::kParams == 2 ? pb[t] : 0.0f, p);
+                const float xh = F::dequant(F::level_at(cr, t), F::kParams >= 1 ? pa[t] : 0.0f, F::kParams == 2 ? pb[t] : 0.0f, p);
 #pragma unroll
                 for (int qq = 0; qq < QB; ++qq) {
                     if (l2) {
@@ -274,20 +302,21 @@ __global__ __launch_bounds__(kScanWaves * 64) void code_scan_kernel(
     }
 }
 
-// Queries per scan workgroup: the queries and the `params` parameter rows share the LDS.
-int code_qb(int d, int params) {
+// Queries per scan workgroup under policy P, before narrowing; 0: d does not fit the LDS.
+int scan_qb(int d, ScanPolicy P) {
     const int64_t per = (int64_t)((d + 3) & ~3) * 4;
-    if (per * (8 + params) <= 128 * 1024) return 8;
-    if (per * (4 + params) <= 128 * 1024) return 4;
-    if (per * (2 + params) <= 128 * 1024) return 2;
-    if (per * (1 + params) <= 160 * 1024) return 1;
+    const int64_t budget = (int64_t)P.lds_kib * 1024;
+    if (per * (8 + P.params) <= budget) return 8;
+    if (per * (4 + P.params) <= budget) return 4;
+    if (per * (2 + P.params) <= budget) return 2;
+    if (per * (1 + P.params) <= 160 * 1024) return 1;
     return 0;
 }
 
 template <int FMT, int R, int QB>
-hipError_t launch_code_scan(const float* q, int64_t nq, const uint8_t* codes, int64_t n, int d, const float* ga,
-                            const float* gb, int metric, int k, int64_t id_offset, int64_t nch, float* pd, uint32_t* pi,
-                            hipStream_t st) {
+hipError_t launch_scan(const float* q, int64_t nq, const uint8_t* codes, int64_t n, int d, const float* ga,
+                       const float* gb, int metric, int k, int64_t id_offset, int64_t nch, float* pd, uint32_t* pi,
+                       hipStream_t st) {
     using F = Fmt<FMT>;
     const size_t smem = (size_t)(QB + F::kParams) * ((d + 3) & ~3) * sizeof(float);
     auto kern = code_scan_kernel<FMT, R, QB>;
@@ -306,31 +335,23 @@ hipError_t launch_code_scan(const float* q, int64_t nq, const uint8_t* codes, in
 // ---------------------------------------------------------------- tiled path
 constexpr int PBM = 128, PBN = 64, PBK = 16, PPAD = 4;
 
-// out[i][j] = the chain of query i against the reconstruction of code row j (pairwise_kernel's
-// tile and loop; IP negated).  `xvec`: 16-B loads of the queries; `cal`: a thread's four
-// dimensions of a row are one aligned load (SQ-8 4 B, SQ-16 8 B, SQ-4 2 B; RaBitQ reads the
-// byte holding its four bits either way).
-template <int FMT, bool IP>
-__global__ __launch_bounds__(256, 2) void code_pairwise_kernel(const float* __restrict__ x, int64_t n,
-                                                            const uint8_t* __restrict__ codes, int64_t m, int d,
-                                                            const float* __restrict__ ga, const float* __restrict__ gb,
-                                                            int xvec, int cal, float* __restrict__ out) {
-    using F = Fmt<FMT>;
+// The tile of both pairwise kernels, for the workgroup's 128 rows of x and 64 rows of y:
+// out[i][j] = L2: fmaf chain over t of (x_i[t] - y_j[t])^2;  IP: -(fmaf chain of x_i[t] y_j[t]).
+// yfetch(t) is dimensions t .. t + 3 (t % 4 == 0) of this thread's y row, row tid >> 2 of the
+// 64.  `xvec`: 16-B loads of x.  UNROLL: the unroll factor of a k-slice, the kernel's choice.
+template <bool IP, int UNROLL, typename YFetch>
+__device__ __forceinline__ void pairwise_tile(const float* x, int64_t n, int64_t m, int d, int xvec, float* out,
+                                              YFetch yfetch) {
     __shared__ __attribute__((aligned(16))) float xs[2][PBK][PBM + PPAD];
     __shared__ __attribute__((aligned(16))) float ys[2][PBK][PBN + PPAD];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int64_t r0 = (int64_t)blockIdx.x * PBM;
     const int64_t c0 = (int64_t)blockIdx.y * PBN;
-
-    // this thread's code row of every slice, and its RaBitQ scale
     const int yrow = tid >> 2, yq4 = tid & 3;
-    const bool yin = c0 + yrow < m;
-    const uint8_t* cr = codes + (yin ? c0 + yrow : 0) * (int64_t)F::row_bytes(d);
-    const float2 p = yin ? F::row_scale(cr, d) : make_float2(0.0f, 0.0f);
 
-    // x slice = 128 rows x 16 t (2 float4 per thread), y slice = 64 rows x 16 t (4 dimensions
-    // per thread, dequantised here); out-of-range rows and dimensions are 0 on both sides,
-    // which leaves every chain unchanged (fmaf(0, 0, a) == a)
+    // global -> register slice loads: x slice = 128 rows x 16 t (2 float4 per thread), y slice =
+    // 64 rows x 16 t (4 dimensions per thread); out-of-range rows and dimensions are 0 on both
+    // sides, which leaves every chain unchanged (fmaf(0, 0, a) == a)
     f32x4 px[2], py;
     auto fetch = [&](int k0) __attribute__((always_inline)) {
 #pragma unroll
@@ -345,8 +366,135 @@ __global__ __launch_bounds__(256, 2) void code_pairwise_kernel(const float* __re
                 for (int j = 0; j < 4; ++j) px[u][j] = (gr < n && t + j < d) ? x[gr * d + t + j] : 0.0f;
             }
         }
-        const int t = k0 + 4 * yq4;
-        py = (f32x4){0.f, 0.f, 0.f, 0.f};
+        py = yfetch(k0 + 4 * yq4);
+    };
+    auto stash = [&](int b) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int f = tid + 256 * u, row = f >> 2, q4 = f & 3;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) xs[b][4 * q4 + j][row] = px[u][j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ys[b][4 * yq4 + j][yrow] = py[j];
+    };
+
+    // scalar fp32 chains: packed fp32 math must not consume LDS-loaded registers (DESIGN.md §8,
+    // tools/isa_audit.py)
+    float acc[8][4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i][0] = acc[i][1] = acc[i][2] = acc[i][3] = 0.0f;
+
+    fetch(0);
+    stash(0);
+    __syncthreads();
+    int b = 0;
+    for (int k0 = 0; k0 < d; k0 += PBK) {
+        const bool more = k0 + PBK < d;
+        if (more) fetch(k0 + PBK);
+#pragma unroll UNROLL
+        for (int t = 0; t < PBK; ++t) {
+            const f32x4 xa = *reinterpret_cast<const f32x4*>(&xs[b][t][ty * 8]);
+            const f32x4 xb = *reinterpret_cast<const f32x4*>(&xs[b][t][ty * 8 + 4]);
+            const f32x4 yv = *reinterpret_cast<const f32x4*>(&ys[b][t][tx * 4]);
+            const float xv[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+            const float yy[4] = {yv.x, yv.y, yv.z, yv.w};
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (IP) {
+                        acc[i][j] = __builtin_fmaf(xv[i], yy[j], acc[i][j]);
+                    } else {
+                        const float df = __fsub_rn(xv[i], yy[j]);
+                        acc[i][j] = __builtin_fmaf(df, df, acc[i][j]);
+                    }
+                }
+            }
+        }
+        if (more) {
+            stash(b ^ 1);
+            __syncthreads();
+            b ^= 1;
+        }
+    }
+    const int64_t gc = c0 + tx * 4;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int64_t gr = r0 + ty * 8 + i;
+        if (gr >= n) continue;
+        f32x4 v = {acc[i][0], acc[i][1], acc[i][2], acc[i][3]};
+        if (IP) v = -v;
+        float* o = out + gr * m + gc;
+        if ((m & 3) == 0 && gc + 3 < m) {
+            *reinterpret_cast<f32x4*>(o) = v;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (gc + j < m) o[j] = v[j];
+        }
+    }
+}
+
+// f32 y: the k-slice fully unrolled (a slice's LDS reads hoisted: ~255 VGPRs, one wave per SIMD).
+template <bool IP, bool VEC>
+__global__ __launch_bounds__(256) void pairwise_kernel(const float* __restrict__ x, int64_t n,
+                                                       const float* __restrict__ y, int64_t m, int d,
+                                                       float* __restrict__ out) {
+    pairwise_tile<IP, PBK>(x, n, m, d, VEC, out, [&](int t) __attribute__((always_inline)) {
+        const int64_t gc = (int64_t)blockIdx.y * PBN + (threadIdx.x >> 2);
+        f32x4 py;
+        if (VEC) {
+            py = (gc < m && t < d) ? *reinterpret_cast<const f32x4*>(y + gc * d + t) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) py[j] = (gc < m && t + j < d) ? y[gc * d + t + j] : 0.0f;
+        }
+        return py;
+    });
+}
+
+void launch_pairwise(const float* x, int64_t n, const float* y, int64_t m, int d, bool ip, hipStream_t st, float* out) {
+    const bool vec = (d % 4) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0;
+    const dim3 grid((unsigned)ceil_div(n, PBM), (unsigned)ceil_div(m, PBN));
+    if (ip) {
+        if (vec) hipLaunchKernelGGL((pairwise_kernel<true, true>), grid, dim3(256), 0, st, x, n, y, m, d, out);
+        else hipLaunchKernelGGL((pairwise_kernel<true, false>), grid, dim3(256), 0, st, x, n, y, m, d, out);
+    } else {
+        if (vec) hipLaunchKernelGGL((pairwise_kernel<false, true>), grid, dim3(256), 0, st, x, n, y, m, d, out);
+        else hipLaunchKernelGGL((pairwise_kernel<false, false>), grid, dim3(256), 0, st, x, n, y, m, d, out);
+    }
+}
+
+// Exact top-k by tiles: pairwise chains for a column chunk, then launch_tiled_topk's
+// segmented top-k and running merge.  Same chains and (dist, id) order as the streaming scan.
+hipError_t launch_flat_tiled(const float* q, int64_t nq, const float* x, int64_t n, int d, int metric, int k,
+                             int64_t id_offset, void* ws, float* dists, uint32_t* ids, hipStream_t st) {
+    const bool ip = metric == MIVQ_METRIC_INNER_PRODUCT;
+    return launch_tiled_topk(nq, n, k, id_offset, ws, dists, ids, st, [&](int64_t c0, int64_t m, float* buf) {
+        launch_pairwise(q, nq, x + c0 * d, m, d, ip, st, buf);
+        return hipGetLastError();
+    });
+}
+
+// The tile against the reconstructions of code rows, dequantised as they are fetched.  `cal`:
+// a thread's four dimensions of a row are one aligned load (SQ-8 4 B, SQ-16 8 B, SQ-4 2 B;
+// RaBitQ reads the byte holding its four bits either way).  The k-slice by 8, not 16: fully
+// unrolled, a slice's LDS reads are hoisted into 256 VGPRs (one wave per SIMD; scratch under a
+// two-wave bound); by 8 it is 77-79 VGPRs at the same speed.
+template <int FMT, bool IP>
+__global__ __launch_bounds__(256, 2) void code_pairwise_kernel(const float* __restrict__ x, int64_t n,
+                                                            const uint8_t* __restrict__ codes, int64_t m, int d,
+                                                            const float* __restrict__ ga, const float* __restrict__ gb,
+                                                            int xvec, int cal, float* __restrict__ out) {
+    using F = Fmt<FMT>;
+    // this thread's code row of every slice, and its RaBitQ scale
+    const int64_t gc = (int64_t)blockIdx.y * PBN + (threadIdx.x >> 2);
+    const bool yin = gc < m;
+    const uint8_t* cr = codes + (yin ? gc : 0) * (int64_t)F::row_bytes(d);
+    const float2 p = yin ? F::row_scale(cr, d) : make_float2(0.0f, 0.0f);
+    pairwise_tile<IP, 8>(x, n, m, d, xvec, out, [&](int t) __attribute__((always_inline)) {
+        f32x4 py = {0.f, 0.f, 0.f, 0.f};
         if (yin && t < d) {
             uint32_t lv[4] = {0u, 0u, 0u, 0u};
             if (F::kIsLvq) {
@@ -391,75 +539,8 @@ __global__ __launch_bounds__(256, 2) void code_pairwise_kernel(const float* __re
                 }
             }
         }
-    };
-    auto stash = [&](int b) __attribute__((always_inline)) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int f = tid + 256 * u, row = f >> 2, q4 = f & 3;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) xs[b][4 * q4 + j][row] = px[u][j];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ys[b][4 * yq4 + j][yrow] = py[j];
-    };
-
-    // scalar fp32 chains: packed fp32 math must not consume LDS-loaded registers (DESIGN.md §8,
-    // tools/isa_audit.py)
-    float acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i][0] = acc[i][1] = acc[i][2] = acc[i][3] = 0.0f;
-
-    fetch(0);
-    stash(0);
-    __syncthreads();
-    int b = 0;
-    for (int k0 = 0; k0 < d; k0 += PBK) {
-        const bool more = k0 + PBK < d;
-        if (more) fetch(k0 + PBK);
-        // by 8, not 16: fully unrolled, a slice's LDS reads are hoisted into 256 VGPRs (one wave
-        // per SIMD; scratch under a two-wave bound); by 8 it is 77-79 VGPRs at the same speed
-#pragma unroll 8
-        for (int t = 0; t < PBK; ++t) {
-            const f32x4 xa = *reinterpret_cast<const f32x4*>(&xs[b][t][ty * 8]);
-            const f32x4 xb = *reinterpret_cast<const f32x4*>(&xs[b][t][ty * 8 + 4]);
-            const f32x4 yv = *reinterpret_cast<const f32x4*>(&ys[b][t][tx * 4]);
-            const float xv[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
-            const float yy[4] = {yv.x, yv.y, yv.z, yv.w};
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (IP) {
-                        acc[i][j] = __builtin_fmaf(xv[i], yy[j], acc[i][j]);
-                    } else {
-                        const float df = __fsub_rn(xv[i], yy[j]);
-                        acc[i][j] = __builtin_fmaf(df, df, acc[i][j]);
-                    }
-                }
-            }
-        }
-        if (more) {
-            stash(b ^ 1);
-            __syncthreads();
-            b ^= 1;
-        }
-    }
-    const int64_t gc = c0 + tx * 4;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int64_t gr = r0 + ty * 8 + i;
-        if (gr >= n) continue;
-        f32x4 v = {acc[i][0], acc[i][1], acc[i][2], acc[i][3]};
-        if (IP) v = -v;
-        float* o = out + gr * m + gc;
-        if ((m & 3) == 0 && gc + 3 < m) {
-            *reinterpret_cast<f32x4*>(o) = v;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (gc + j < m) o[j] = v[j];
-        }
-    }
+        return py;
+    });
 }
 
 template <int FMT>
@@ -482,26 +563,30 @@ hipError_t launch_code_tiled(const float* q, int64_t nq, const uint8_t* codes, i
 }
 
 // ---------------------------------------------------------------- workspace + dispatch
-// The workspace of a code search (nq, n > 0): the tiled path's (laid out by launch_tiled_topk:
+// The tiled path (pairwise chains + segmented top-k) wins once there are enough queries to
+// fill a 128-row tile; the streaming scan keeps the small-batch cases.
+bool flat_use_tiled(int64_t nq, int64_t n) { return nq >= 16 && n >= 4096; }
+
+// The workspace of an exact search (nq, n > 0): the tiled path's (laid out by launch_tiled_topk:
 // key block + part lists), or the streaming scan's part lists (parts, nq, k) of distances at
 // pd and ids at pi.  Never decoded rows.  QB == 0 on the streaming path: d does not fit LDS.
-struct CodeSearchLayout {
+struct SearchLayout {
     bool tiled;
     int QB;
     int64_t nch, parts;
     size_t pd, pi, total;
 };
 
-CodeSearchLayout code_search_layout(int64_t nq, int64_t n, int d, int k, int params) {
-    CodeSearchLayout L{};
+SearchLayout search_layout(int64_t nq, int64_t n, int d, int k, ScanPolicy P) {
+    SearchLayout L{};
     L.tiled = flat_use_tiled(nq, n);
-    L.QB = code_qb(d, params);
+    L.QB = scan_qb(d, P);
     if (L.tiled) {
         L.total = flat_tiled_workspace_bytes(nq, n, k);
     } else if (L.QB > 0) {
         // no wider than the batch: a workgroup computes all QB chains of a row, and the scan is
         // bound by the LDS reads of the queries (nq = 1 at QB = 8: 2.5 ms per 1M x 3072 SQ-8)
-        while (L.QB > 1 && L.QB / 2 >= nq) L.QB /= 2;
+        while (P.narrow && L.QB > 1 && L.QB / 2 >= nq) L.QB /= 2;
         L.nch = adc_chunks(nq, n, L.QB);
         L.parts = L.nch * kScanWaves;
         const size_t list = align_up((size_t)L.parts * nq * k * 4, 256);
@@ -512,17 +597,27 @@ CodeSearchLayout code_search_layout(int64_t nq, int64_t n, int d, int k, int par
     return L;
 }
 
-// Shared body of the two entry points (arguments validated up to the format's own).
+size_t search_workspace_bytes(int64_t nq, int64_t n, int d, int k, ScanPolicy P) {
+    if (nq <= 0 || n <= 0 || d <= 0 || k <= 0) return 0;
+    return search_layout(nq, n, d, k, P).total;
+}
+
+// Shared body of the entry points (arguments validated up to the format's own); an f32
+// database arrives as its bytes.
 template <int FMT>
-int code_flat_search(const char* name, const float* q, int64_t nq, const uint8_t* codes, int64_t n, int d,
-                     const float* ga, const float* gb, int metric, int k, int64_t id_offset, void* workspace,
-                     size_t workspace_bytes, float* dists, uint32_t* ids, hipStream_t st) {
+int exact_flat_search(const char* name, const float* q, int64_t nq, const uint8_t* codes, int64_t n, int d,
+                      const float* ga, const float* gb, int metric, int k, int64_t id_offset, void* workspace,
+                      size_t workspace_bytes, float* dists, uint32_t* ids, hipStream_t st) {
     using F = Fmt<FMT>;
-    const CodeSearchLayout L = code_search_layout(nq, n, d, k, F::kParams);
+    const SearchLayout L = search_layout(nq, n, d, k, F::kPolicy);
     MIVQ_REQUIRE(workspace && workspace_bytes >= L.total, MIVQ_ERR_WORKSPACE, "%s: workspace %zu < %zu", name,
                  workspace_bytes, L.total);
     if (L.tiled) {
-        const hipError_t et = launch_code_tiled<FMT>(q, nq, codes, n, d, ga, gb, metric, k, id_offset, workspace, dists, ids, st);
+        hipError_t et;
+        if constexpr (FMT == kF32)
+            et = launch_flat_tiled(q, nq, reinterpret_cast<const float*>(codes), n, d, metric, k, id_offset, workspace, dists, ids, st);
+        else
+            et = launch_code_tiled<FMT>(q, nq, codes, n, d, ga, gb, metric, k, id_offset, workspace, dists, ids, st);
         if (et != hipSuccess) return set_error(MIVQ_ERR_HIP, "%s (tiled): %s", name, hipGetErrorString(et));
         return MIVQ_OK;
     }
@@ -531,26 +626,28 @@ int code_flat_search(const char* name, const float* q, int64_t nq, const uint8_t
     uint32_t* pi = reinterpret_cast<uint32_t*>(ws + L.pi);
     hipError_t e = with_topk_regs(k, [&](auto R) {
         return with_query_block(L.QB, [&](auto QB) {
-            return launch_code_scan<FMT, decltype(R)::value, decltype(QB)::value>(q, nq, codes, n, d, ga, gb, metric, k,
-                                                                                  id_offset, L.nch, pd, pi, st);
+            return launch_scan<FMT, decltype(R)::value, decltype(QB)::value>(q, nq, codes, n, d, ga, gb, metric, k,
+                                                                             id_offset, L.nch, pd, pi, st);
         });
     });
+    // (mivq_flat_search words its two launch failures its own way)
+    if (e != hipSuccess && FMT == kF32) return set_error(MIVQ_ERR_HIP, "flat_scan: %s", hipGetErrorString(e));
     if (e != hipSuccess) return set_error(MIVQ_ERR_HIP, "%s (scan): %s", name, hipGetErrorString(e));
     e = launch_topk_merge(pd, pi, (int)L.parts, nq, k, dists, ids, st);
+    if (e != hipSuccess && FMT == kF32) return set_error(MIVQ_ERR_HIP, "topk_merge: %s", hipGetErrorString(e));
     if (e != hipSuccess) return set_error(MIVQ_ERR_HIP, "%s (merge): %s", name, hipGetErrorString(e));
     return MIVQ_OK;
 }
 
-// The checks every code search shares with mivq_flat_search, in its order; *done is set when
-// the call is complete without a scan (nq == 0, or n == 0: sentinel lists).
-int code_search_prologue(const char* name, int64_t nq, int64_t n, int d, int params, int metric, int k, int64_t id_offset,
-                         float* dists, uint32_t* ids, hipStream_t st, bool* done) {
+// The checks every exact search shares, in mivq_flat_search's order; *done is set when the
+// call is complete without a scan (nq == 0, or n == 0: sentinel lists).
+int search_prologue(const char* name, int64_t nq, int64_t n, int d, ScanPolicy P, int metric, int k, int64_t id_offset,
+                    float* dists, uint32_t* ids, hipStream_t st, bool* done) {
     *done = false;
     MIVQ_REQUIRE(k <= 256, MIVQ_ERR_UNSUPPORTED, "%s: k=%d > 256", name, k);
     MIVQ_REQUIRE(metric == MIVQ_METRIC_L2 || metric == MIVQ_METRIC_INNER_PRODUCT, MIVQ_ERR_UNSUPPORTED, "%s: metric %d",
                  name, metric);
-    MIVQ_REQUIRE(code_qb(d, params) > 0 || flat_use_tiled(nq, n), MIVQ_ERR_UNSUPPORTED, "%s: d=%d too large for LDS", name,
-                 d);
+    MIVQ_REQUIRE(scan_qb(d, P) > 0 || flat_use_tiled(nq, n), MIVQ_ERR_UNSUPPORTED, "%s: d=%d too large for LDS", name, d);
     MIVQ_REQUIRE(id_offset >= 0 && id_offset + n <= (int64_t)kNoId, MIVQ_ERR_INVALID, "%s: ids overflow", name);
     if (nq == 0) {
         *done = true;
@@ -570,19 +667,46 @@ int code_search_prologue(const char* name, int64_t nq, int64_t n, int d, int par
 
 using namespace mivq;
 
+extern "C" int mivq_pairwise_distances(const float* x, int64_t n, const float* y, int64_t m, int32_t d,
+                                       int32_t metric, float* out, void* stream) {
+    MIVQ_REQUIRE(n >= 0 && m >= 0 && d > 0, MIVQ_ERR_INVALID, "pairwise_distances: bad sizes");
+    MIVQ_REQUIRE(metric == MIVQ_METRIC_L2 || metric == MIVQ_METRIC_INNER_PRODUCT, MIVQ_ERR_UNSUPPORTED,
+                 "pairwise_distances: metric %d", metric);
+    MIVQ_REQUIRE(ceil_div(m, PBN) <= 65535, MIVQ_ERR_UNSUPPORTED, "pairwise_distances: m=%lld too large",
+                 (long long)m);
+    if (n == 0 || m == 0) return MIVQ_OK;
+    MIVQ_REQUIRE(x && y && out, MIVQ_ERR_INVALID, "pairwise_distances: null pointer");
+    launch_pairwise(x, n, y, m, d, metric == MIVQ_METRIC_INNER_PRODUCT, as_stream(stream), out);
+    return check_launch("pairwise_distances");
+}
+
+extern "C" size_t mivq_flat_search_workspace_bytes(int64_t nq, int64_t n, int32_t d, int32_t k) {
+    return search_workspace_bytes(nq, n, d, k, Fmt<kF32>::kPolicy);
+}
+
 extern "C" size_t mivq_sq_flat_search_workspace_bytes(int64_t nq, int64_t n, int32_t d, int32_t k) {
-    if (nq <= 0 || n <= 0 || d <= 0 || k <= 0) return 0;
-    return code_search_layout(nq, n, d, k, 2).total;
+    return search_workspace_bytes(nq, n, d, k, Fmt<kSq8>::kPolicy);
 }
 
 extern "C" size_t mivq_rabitq_flat_search_workspace_bytes(int64_t nq, int64_t n, int32_t d, int32_t k) {
-    if (nq <= 0 || n <= 0 || d <= 0 || k <= 0) return 0;
-    return code_search_layout(nq, n, d, k, 1).total;
+    return search_workspace_bytes(nq, n, d, k, Fmt<kRbq>::kPolicy);
 }
 
 extern "C" size_t mivq_lvq_flat_search_workspace_bytes(int64_t nq, int64_t n, int32_t d, int32_t k) {
-    if (nq <= 0 || n <= 0 || d <= 0 || k <= 0) return 0;
-    return code_search_layout(nq, n, d, k, 1).total;
+    return search_workspace_bytes(nq, n, d, k, Fmt<kLvq>::kPolicy);
+}
+
+extern "C" int mivq_flat_search(const float* q, int64_t nq, const float* x, int64_t n, int32_t d, int32_t metric,
+                                int32_t k, int64_t id_offset, void* workspace, size_t workspace_bytes, float* dists,
+                                uint32_t* ids, void* stream) {
+    MIVQ_REQUIRE(nq >= 0 && n >= 0 && d > 0 && k > 0, MIVQ_ERR_INVALID, "flat_search: bad sizes");
+    hipStream_t st = as_stream(stream);
+    bool done = false;
+    const int rc = search_prologue("flat_search", nq, n, d, Fmt<kF32>::kPolicy, metric, k, id_offset, dists, ids, st, &done);
+    if (rc != MIVQ_OK || done) return rc;
+    MIVQ_REQUIRE(q && x, MIVQ_ERR_INVALID, "flat_search: null pointer");
+    return exact_flat_search<kF32>("flat_search", q, nq, reinterpret_cast<const uint8_t*>(x), n, d, nullptr, nullptr, metric,
+                                   k, id_offset, workspace, workspace_bytes, dists, ids, st);
 }
 
 extern "C" int mivq_sq_flat_search(const float* q, int64_t nq, const void* codes, int64_t n, int32_t d, const float* lo,
@@ -592,19 +716,19 @@ extern "C" int mivq_sq_flat_search(const float* q, int64_t nq, const void* codes
     MIVQ_REQUIRE(nbits == 4 || nbits == 8 || nbits == 16, MIVQ_ERR_INVALID, "num_bits must be 4, 8, or 16, got %d", nbits);
     hipStream_t st = as_stream(stream);
     bool done = false;
-    const int rc = code_search_prologue("sq_flat_search", nq, n, d, 2, metric, k, id_offset, dists, ids, st, &done);
+    const int rc = search_prologue("sq_flat_search", nq, n, d, Fmt<kSq8>::kPolicy, metric, k, id_offset, dists, ids, st, &done);
     if (rc != MIVQ_OK || done) return rc;
     MIVQ_REQUIRE(q && codes && lo && den, MIVQ_ERR_INVALID, "sq_flat_search: null pointer");
     MIVQ_REQUIRE(nbits != 16 || reinterpret_cast<uintptr_t>(codes) % 2 == 0, MIVQ_ERR_INVALID,
                  "sq_flat_search: 16-bit codes must be 2-byte aligned");
     const uint8_t* c = static_cast<const uint8_t*>(codes);
     if (nbits == 4)
-        return code_flat_search<kSq4>("sq_flat_search", q, nq, c, n, d, den, lo, metric, k, id_offset, workspace,
+        return exact_flat_search<kSq4>("sq_flat_search", q, nq, c, n, d, den, lo, metric, k, id_offset, workspace,
                                       workspace_bytes, dists, ids, st);
     if (nbits == 8)
-        return code_flat_search<kSq8>("sq_flat_search", q, nq, c, n, d, den, lo, metric, k, id_offset, workspace,
+        return exact_flat_search<kSq8>("sq_flat_search", q, nq, c, n, d, den, lo, metric, k, id_offset, workspace,
                                       workspace_bytes, dists, ids, st);
-    return code_flat_search<kSq16>("sq_flat_search", q, nq, c, n, d, den, lo, metric, k, id_offset, workspace,
+    return exact_flat_search<kSq16>("sq_flat_search", q, nq, c, n, d, den, lo, metric, k, id_offset, workspace,
                                    workspace_bytes, dists, ids, st);
 }
 
@@ -614,10 +738,10 @@ extern "C" int mivq_rabitq_flat_search(const float* q, int64_t nq, const uint8_t
     MIVQ_REQUIRE(nq >= 0 && n >= 0 && d > 0 && k > 0, MIVQ_ERR_INVALID, "rabitq_flat_search: bad sizes");
     hipStream_t st = as_stream(stream);
     bool done = false;
-    const int rc = code_search_prologue("rabitq_flat_search", nq, n, d, 1, metric, k, id_offset, dists, ids, st, &done);
+    const int rc = search_prologue("rabitq_flat_search", nq, n, d, Fmt<kRbq>::kPolicy, metric, k, id_offset, dists, ids, st, &done);
     if (rc != MIVQ_OK || done) return rc;
     MIVQ_REQUIRE(q && codes, MIVQ_ERR_INVALID, "rabitq_flat_search: null pointer");
-    return code_flat_search<kRbq>("rabitq_flat_search", q, nq, codes, n, d, centroid, nullptr, metric, k, id_offset,
+    return exact_flat_search<kRbq>("rabitq_flat_search", q, nq, codes, n, d, centroid, nullptr, metric, k, id_offset,
                                   workspace, workspace_bytes, dists, ids, st);
 }
 
@@ -628,12 +752,12 @@ extern "C" int mivq_lvq_flat_search(const float* q, int64_t nq, const uint8_t* c
     MIVQ_REQUIRE(nbits >= 1 && nbits <= 8, MIVQ_ERR_INVALID, "num_bits must be in [1, 8], got %d", nbits);
     hipStream_t st = as_stream(stream);
     bool done = false;
-    const int rc = code_search_prologue("lvq_flat_search", nq, n, d, 1, metric, k, id_offset, dists, ids, st, &done);
+    const int rc = search_prologue("lvq_flat_search", nq, n, d, Fmt<kLvq>::kPolicy, metric, k, id_offset, dists, ids, st, &done);
     if (rc != MIVQ_OK || done) return rc;
     MIVQ_REQUIRE(q && codes && mu, MIVQ_ERR_INVALID, "lvq_flat_search: null pointer");
 #define MIVQ_LVQ_SEARCH(B)                                                                                             \
     case B:                                                                                                            \
-        return code_flat_search<kLvq + B - 1>("lvq_flat_search", q, nq, codes, n, d, mu, nullptr, metric, k, id_offset, \
+        return exact_flat_search<kLvq + B - 1>("lvq_flat_search", q, nq, codes, n, d, mu, nullptr, metric, k, id_offset, \
                                               workspace, workspace_bytes, dists, ids, st)
     switch (nbits) {
         MIVQ_LVQ_SEARCH(1);

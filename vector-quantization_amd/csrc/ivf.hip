@@ -4,13 +4,11 @@
 // faiss_ivfpq_index.py:46-76: faiss IndexIVFPQ over an IndexFlatL2 / IndexFlatIP coarse
 // quantizer, residual PQ) and of the IVF build timed in benchmarks/ivf_benchmark.py:170-204.
 //
-//   pairwise_kernel        exact coarse distances (the quantizer's exhaustive search and the
-//                          k-means assignment): 128 x 64 (row, centroid) tile per 256-thread
-//                          workgroup, 8 x 4 per thread as 16 v_pk chains, k-slices of 16
-//                          staged transposed in LDS (double-buffered, prefetched into
-//                          registers one slice ahead).  Every (row, centroid) value is one
-//                          sequential fmaf chain over t, the same as mivq_flat_search.
-//   topk_rows_kernel       per-row (value, column) top-k (wave per row; k = 1 is a plain
+// The exact coarse distances (the quantizer's exhaustive search and the k-means assignment)
+// are mivq_pairwise_distances, exact_search.hip's pairwise_kernel: every (row, centroid) value
+// is one sequential scalar fmaf chain over t, the same as mivq_flat_search.
+//
+//   topk_rows_kernel      per-row (value, column) top-k (wave per row; k = 1 is a plain
 //                          lane-strided argmin plus one wave reduction).
 //   bucket_*               stable counting sort of list assignments (per-block histograms,
 //                          column prefix, block-local ranks by wave match loops), giving
@@ -26,120 +24,6 @@
 
 namespace mivq {
 namespace {
-
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int PBM = 128, PBN = 64, PBK = 16, PPAD = 4;
-
-// out[i][j] = L2: fmaf chain over t of (x_i[t] - y_j[t])^2;  IP: -(fmaf chain of x_i[t] y_j[t])
-template <bool IP, bool VEC>
-__global__ __launch_bounds__(256) void pairwise_kernel(const float* __restrict__ x, int64_t n,
-                                                       const float* __restrict__ y, int64_t m, int d,
-                                                       float* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) float xs[2][PBK][PBM + PPAD];
-    __shared__ __attribute__((aligned(16))) float ys[2][PBK][PBN + PPAD];
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const int64_t r0 = (int64_t)blockIdx.x * PBM;
-    const int64_t c0 = (int64_t)blockIdx.y * PBN;
-
-    // global -> register slice loads: x slice = 128 rows x 16 t (2 float4 per thread),
-    // y slice = 64 rows x 16 t (1 float4 per thread); out-of-range values are 0, which
-    // leaves every chain unchanged (fmaf(0, 0, a) == a)
-    f32x4 px[2], py;
-    auto fetch = [&](int k0) __attribute__((always_inline)) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int f = tid + 256 * u, row = f >> 2, q4 = f & 3;
-            const int64_t gr = r0 + row;
-            const int t = k0 + 4 * q4;
-            if (VEC) {
-                px[u] = (gr < n && t < d) ? *reinterpret_cast<const f32x4*>(x + gr * d + t) : (f32x4){0.f, 0.f, 0.f, 0.f};
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) px[u][j] = (gr < n && t + j < d) ? x[gr * d + t + j] : 0.0f;
-            }
-        }
-        {
-            const int row = tid >> 2, q4 = tid & 3;
-            const int64_t gc = c0 + row;
-            const int t = k0 + 4 * q4;
-            if (VEC) {
-                py = (gc < m && t < d) ? *reinterpret_cast<const f32x4*>(y + gc * d + t) : (f32x4){0.f, 0.f, 0.f, 0.f};
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) py[j] = (gc < m && t + j < d) ? y[gc * d + t + j] : 0.0f;
-            }
-        }
-    };
-    auto stash = [&](int b) __attribute__((always_inline)) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int f = tid + 256 * u, row = f >> 2, q4 = f & 3;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) xs[b][4 * q4 + j][row] = px[u][j];
-        }
-        const int row = tid >> 2, q4 = tid & 3;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ys[b][4 * q4 + j][row] = py[j];
-    };
-
-    // scalar fp32 chains: packed fp32 math must not consume LDS-loaded registers (DESIGN.md §8,
-    // tools/isa_audit.py)
-    float acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i][0] = acc[i][1] = acc[i][2] = acc[i][3] = 0.0f;
-
-    fetch(0);
-    stash(0);
-    __syncthreads();
-    int b = 0;
-    for (int k0 = 0; k0 < d; k0 += PBK) {
-        const bool more = k0 + PBK < d;
-        if (more) fetch(k0 + PBK);
-#pragma unroll
-        for (int t = 0; t < PBK; ++t) {
-            const f32x4 xa = *reinterpret_cast<const f32x4*>(&xs[b][t][ty * 8]);
-            const f32x4 xb = *reinterpret_cast<const f32x4*>(&xs[b][t][ty * 8 + 4]);
-            const f32x4 yv = *reinterpret_cast<const f32x4*>(&ys[b][t][tx * 4]);
-            const float xv[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
-            const float yy[4] = {yv.x, yv.y, yv.z, yv.w};
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (IP) {
-                        acc[i][j] = __builtin_fmaf(xv[i], yy[j], acc[i][j]);
-                    } else {
-                        const float df = __fsub_rn(xv[i], yy[j]);
-                        acc[i][j] = __builtin_fmaf(df, df, acc[i][j]);
-                    }
-                }
-            }
-        }
-        if (more) {
-            stash(b ^ 1);
-            __syncthreads();
-            b ^= 1;
-        }
-    }
-    const int64_t gc = c0 + tx * 4;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int64_t gr = r0 + ty * 8 + i;
-        if (gr >= n) continue;
-        f32x4 v = {acc[i][0], acc[i][1], acc[i][2], acc[i][3]};
-        if (IP) v = -v;
-        float* o = out + gr * m + gc;
-        if ((m & 3) == 0 && gc + 3 < m) {
-            *reinterpret_cast<f32x4*>(o) = v;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (gc + j < m) o[j] = v[j];
-        }
-    }
-}
 
 // Per row: the k smallest (value, column) pairs.  Wave per row, 4 rows per block.
 template <int R>
@@ -410,30 +294,6 @@ __global__ __launch_bounds__(kIvfWaves * 64) void ivfpq_scan_kernel(
     top.store(part_d + (part * nq + q) * k, part_i + (part * nq + q) * k, k, lane);
 }
 
-}  // namespace
-
-// Exact top-k by tiles: pairwise chains for a column chunk, then launch_tiled_topk's
-// segmented top-k and running merge.  Same chains and (dist, id) order as flat_scan.
-hipError_t launch_flat_tiled(const float* q, int64_t nq, const float* x, int64_t n, int d, int metric, int k,
-                             int64_t id_offset, void* ws, float* dists, uint32_t* ids, hipStream_t st) {
-    const bool vec = (d % 4) == 0 && ((uintptr_t)q % 16) == 0 && ((uintptr_t)x % 16) == 0;
-    const bool ip = metric == MIVQ_METRIC_INNER_PRODUCT;
-    return launch_tiled_topk(nq, n, k, id_offset, ws, dists, ids, st, [&](int64_t c0, int64_t m, float* buf) {
-        const dim3 grid((unsigned)ceil_div(nq, PBM), (unsigned)ceil_div(m, PBN));
-        const float* y = x + c0 * d;
-        if (ip) {
-            if (vec) hipLaunchKernelGGL((pairwise_kernel<true, true>), grid, dim3(256), 0, st, q, nq, y, m, d, buf);
-            else hipLaunchKernelGGL((pairwise_kernel<true, false>), grid, dim3(256), 0, st, q, nq, y, m, d, buf);
-        } else {
-            if (vec) hipLaunchKernelGGL((pairwise_kernel<false, true>), grid, dim3(256), 0, st, q, nq, y, m, d, buf);
-            else hipLaunchKernelGGL((pairwise_kernel<false, false>), grid, dim3(256), 0, st, q, nq, y, m, d, buf);
-        }
-        return hipGetLastError();
-    });
-}
-
-namespace {
-
 int ivf_splits(int64_t nq, int nprobe) {
     const int64_t want = ceil_div(512, std::max<int64_t>(nq, 1));
     const int64_t maxs = ceil_div(nprobe, kIvfWaves);
@@ -471,29 +331,6 @@ unsigned grid_for(int64_t total) {
 }  // namespace mivq
 
 using namespace mivq;
-
-extern "C" int mivq_pairwise_distances(const float* x, int64_t n, const float* y, int64_t m, int32_t d,
-                                       int32_t metric, float* out, void* stream) {
-    MIVQ_REQUIRE(n >= 0 && m >= 0 && d > 0, MIVQ_ERR_INVALID, "pairwise_distances: bad sizes");
-    MIVQ_REQUIRE(metric == MIVQ_METRIC_L2 || metric == MIVQ_METRIC_INNER_PRODUCT, MIVQ_ERR_UNSUPPORTED,
-                 "pairwise_distances: metric %d", metric);
-    MIVQ_REQUIRE(ceil_div(m, PBN) <= 65535, MIVQ_ERR_UNSUPPORTED, "pairwise_distances: m=%lld too large",
-                 (long long)m);
-    if (n == 0 || m == 0) return MIVQ_OK;
-    MIVQ_REQUIRE(x && y && out, MIVQ_ERR_INVALID, "pairwise_distances: null pointer");
-    const bool vec = (d % 4) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0;
-    const dim3 grid((unsigned)ceil_div(n, PBM), (unsigned)ceil_div(m, PBN));
-    hipStream_t st = as_stream(stream);
-    const bool ip = metric == MIVQ_METRIC_INNER_PRODUCT;
-    if (ip) {
-        if (vec) hipLaunchKernelGGL((pairwise_kernel<true, true>), grid, dim3(256), 0, st, x, n, y, m, d, out);
-        else hipLaunchKernelGGL((pairwise_kernel<true, false>), grid, dim3(256), 0, st, x, n, y, m, d, out);
-    } else {
-        if (vec) hipLaunchKernelGGL((pairwise_kernel<false, true>), grid, dim3(256), 0, st, x, n, y, m, d, out);
-        else hipLaunchKernelGGL((pairwise_kernel<false, false>), grid, dim3(256), 0, st, x, n, y, m, d, out);
-    }
-    return check_launch("pairwise_distances");
-}
 
 extern "C" int mivq_topk_rows(const float* dist, int64_t n, int64_t m, int32_t k, float* out_d, uint32_t* out_i,
                               void* stream) {

@@ -114,13 +114,7 @@ hipError_t launch_tiled_topk(int64_t nq, int64_t n, int k, int64_t id_offset, vo
 // Columns per key block of launch_tiled_topk (a multiple of its 4096-column segment; the key
 // block is nq x that many floats at the start of its workspace).
 int64_t tiled_topk_cols(int64_t nq, int64_t n);
-// Workspace of the tiled exact brute force (topk.hip), and its launcher (ivf.hip, beside the
-// pairwise kernel k-means shares): pairwise chains + segmented top-k + running merge.
+// Workspace of the tiled exact brute force (exact_search.hip: pairwise chains as the TileFn).
 size_t flat_tiled_workspace_bytes(int64_t nq, int64_t n, int k);
-// Which of the two exact flat paths a search of this shape takes (flat_search.hip); the f32
-// search and the code searches (code_search.hip) share the choice.
-bool flat_use_tiled(int64_t nq, int64_t n);
-hipError_t launch_flat_tiled(const float* q, int64_t nq, const float* x, int64_t n, int d, int metric, int k,
-                             int64_t id_offset, void* ws, float* dists, uint32_t* ids, hipStream_t st);
 
 }  // namespace mivq
