@@ -176,7 +176,9 @@ int mivq_rabitq_decode(const uint8_t* codes, int64_t n, int32_t d, const float* 
  * oracle/mivq_oracle.c oracle_rabitq_est).  dists/ids: (nq, k) ascending keys, ties to the
  * smaller id; L2 keys are the distance estimates, INNER_PRODUCT keys the negated
  * inner-product estimates.  ids = id_offset + row.  Workspace from
- * mivq_rabitq_search_workspace_bytes. */
+ * mivq_rabitq_search_workspace_bytes.  With qb = 0, d % 32 != 0 or codes not 4-byte aligned
+ * (the generic estimator, whose grid is (code blocks, nq)) a call takes nq <= 65535 queries
+ * and returns MIVQ_ERR_UNSUPPORTED above that, before any launch; pass ranges of queries. */
 size_t mivq_rabitq_search_workspace_bytes(int64_t nq, int64_t n, int32_t d, int32_t k);
 int mivq_rabitq_search(const uint8_t* codes, int64_t n, int32_t d, const float* centroid,
                        const float* q, int64_t nq, int32_t qb, int32_t metric, int32_t k,
@@ -269,7 +271,9 @@ int mivq_lvq_flat_search(const float* q, int64_t nq, const uint8_t* codes, int64
                          int64_t id_offset, void* workspace, size_t workspace_bytes, float* dists,
                          uint32_t* ids, void* stream);
 /* Merges `parts` sorted (nq, k) lists laid out (parts, nq, k) into one sorted (nq, k) list
- * with the same (dist, id) order — the on-device merge after the RCCL all-gather. */
+ * with the same (dist, id) order (ids compared as uint32, NaN dists ranked and written as +inf)
+ * — the on-device merge after the RCCL all-gather.  parts == 0 writes (+inf, 0xFFFFFFFF)
+ * everywhere; k in [1, 256]. */
 int mivq_topk_merge(const float* dists_in, const uint32_t* ids_in, int32_t parts, int64_t nq,
                     int32_t k, float* dists_out, uint32_t* ids_out, void* stream);
 
@@ -319,7 +323,15 @@ int mivq_ivfpq_terms(const uint8_t* codes, int64_t n, int32_t d, int32_t M, int3
  *   S = ((lut[q][0][c_0] + lut[q][1][c_1]) + ...) + lut[q][M-1][c_{M-1}]
  *   L2: dist = (probe_d + tau) + 2 * S  (= ||q - coarse_l - r_hat||^2 expanded)
  *   IP: dist = probe_d + S              (= -(q . coarse_l + q . r_hat))
- * ranked like mivq_adc_search: ascending (dist, id) with id = the list_ids entry. */
+ * ranked like mivq_adc_search: ascending (dist, id) with id = the list_ids entry compared as
+ * uint32, so ids >= 2^31 rank after the smaller ones.  A NaN dist ranks as +inf and keeps its
+ * id; dists/ids (nq, k) are padded with (+inf, 0xFFFFFFFF) when fewer than k rows are probed
+ * (skipped slots, empty lists), the pads after every real row.  The result does not depend on
+ * the order of a query's probe slots.
+ * Limits, checked on the host before any launch (MIVQ_ERR_UNSUPPORTED): k in [1, 256];
+ * nbits in [1, 8]; M * 2^nbits * 4 <= 128 KiB (the query's table lives in LDS: M <= 128 at
+ * nbits = 8); nq <= 65535 per call (the scan's grid is (probe splits, nq); a caller with more
+ * queries passes ranges of them: queries are independent, so the rows are those of one call). */
 size_t mivq_ivfpq_search_workspace_bytes(int64_t nq, int32_t nprobe, int32_t k);
 int mivq_ivfpq_search(const float* lut, int64_t nq, int32_t M, int32_t nbits, const float* probe_d,
                       const uint32_t* probe_l, int32_t nprobe, int32_t nlist, const int64_t* offsets,

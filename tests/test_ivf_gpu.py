@@ -143,6 +143,8 @@ def test_ivfpq_terms_bit_exact(dev, oracle, d, M, nbits):
     (2000, 96, 50, 16, 8, 50, 100),   # nprobe = K: every list
     (256, 16, 8, 4, 4, 4, 4),         # the reference test's shape
     (1500, 1536, 64, 16, 8, 16, 10),  # headline dimensionality
+    (1200, 48, 12, 6, 8, 5, 10),      # M % 4 != 0: the scan's byte path and the torch-indexing branch of add
+    (900, 30, 9, 10, 3, 9, 10),       # nbits = 3: pq_unpack on the add path, M % 4 != 0
 ])
 def test_ivfpq_pipeline_bit_exact(dev, oracle, metric, n, d, K, M, nbits, nprobe, k):
     """Same coarse centroids and codebooks -> identical lists and (dist, id) results."""
@@ -172,6 +174,38 @@ def test_ivfpq_pipeline_bit_exact(dev, oracle, metric, n, d, K, M, nbits, nprobe
     rd, ri = oracle.ivfpq_query(Q, coarse, Cpq, built, nprobe, k, metric)
     np.testing.assert_array_equal(_h(ii).view(np.uint32), ri)
     np.testing.assert_array_equal(_h(dd), rd)
+
+
+@pytest.mark.parametrize("metric", [1, 0])
+def test_ivfpq_empty_list_and_k_above_ntotal(dev, oracle, metric):
+    """A coarse centroid no row is assigned to (far from positive data under L2, the most negative
+    product under IP): its list is empty, every list is probed, and k = 40 > ntotal = 30 pads."""
+    from haag_vq import _native
+    from haag_vq.methods._ivf import IvfPq
+
+    n, d, K, M, nbits, k, dead = 30, 16, 5, 4, 4, 40, 2
+    rng = np.random.default_rng(30)
+    X = (np.abs(rng.standard_normal((n, d))) + 1.0).astype(np.float32)
+    Q = (np.abs(rng.standard_normal((7, d))) + 1.0).astype(np.float32)
+    coarse = X[rng.choice(n, K, replace=False)].copy()
+    coarse[dead] = -10.0
+    Cpq = (0.3 * rng.standard_normal((M, 1 << nbits, d // M))).astype(np.float32)
+    idx = IvfPq(d, K, M, nbits, metric)
+    idx.coarse = _t(coarse, dev)
+    idx.pq = _t(Cpq, dev)
+    idx.prep = _native.pq_prepare(idx.pq, nbits)
+    idx.add(_t(X, dev))
+    built = oracle.ivfpq_build(X, coarse, Cpq, metric)
+    offsets = _h(idx.lists.offsets)
+    np.testing.assert_array_equal(offsets, built[2])
+    assert offsets[dead + 1] == offsets[dead] and offsets[-1] == n
+    dd, ii = idx.search(_t(Q, dev), k, K)
+    rd, ri = oracle.ivfpq_query(Q, coarse, Cpq, built, K, k, metric)
+    ii = _h(ii).view(np.uint32)
+    np.testing.assert_array_equal(ii, ri)
+    np.testing.assert_array_equal(_h(dd).view(np.uint32), rd.view(np.uint32))
+    assert (np.sort(ii[:, :n], axis=1) == np.arange(n)).all()  # every row once, then padding
+    assert (ii[:, n:] == _native.NO_ID).all() and np.isposinf(_h(dd)[:, n:]).all()
 
 
 def test_ivfpq_incremental_add_matches_single_add(dev):

@@ -443,6 +443,8 @@ extern "C" int mivq_ivfpq_search(const float* lut, int64_t nq, int32_t M, int32_
                  "ivfpq_search: metric %d", metric);
     const int ksub = 1 << nbits;
     MIVQ_REQUIRE((int64_t)M * ksub * 4 <= 128 * 1024, MIVQ_ERR_UNSUPPORTED, "ivfpq_search: M*ksub too large for LDS");
+    // the scan's grid is (splits, nq) and grid.y is limited to 65535: larger batches are the caller's to split
+    MIVQ_REQUIRE(nq <= 65535, MIVQ_ERR_UNSUPPORTED, "ivfpq_search: nq=%lld > 65535 queries per call", (long long)nq);
     if (nq == 0) return MIVQ_OK;
     const bool l2 = metric == MIVQ_METRIC_L2;
     MIVQ_REQUIRE(lut && probe_d && probe_l && offsets && list_codes && list_ids && dists && ids && (!l2 || tau),

@@ -582,6 +582,11 @@ extern "C" int mivq_rabitq_search(const uint8_t* codes, int64_t n, int32_t d, co
     if (nq == 0) return MIVQ_OK;
     MIVQ_REQUIRE(q && dists && ids && workspace, MIVQ_ERR_INVALID, "rabitq_search: null pointer");
     MIVQ_REQUIRE(n == 0 || codes, MIVQ_ERR_INVALID, "rabitq_search: null codes");
+    const bool mfma = qb > 0 && (d % 32) == 0 && (reinterpret_cast<uintptr_t>(codes) % 4) == 0;
+    // the generic estimator's grid is (code blocks, nq) and grid.y is limited to 65535
+    MIVQ_REQUIRE(n == 0 || mfma || nq <= 65535, MIVQ_ERR_UNSUPPORTED,
+                 "rabitq_search: nq=%lld > 65535 queries per call (qb = 0, d %% 32 != 0 or unaligned codes)",
+                 (long long)nq);
     const RqLayout L = rq_layout(nq, n, d, k);
     MIVQ_REQUIRE(workspace_bytes >= L.total, MIVQ_ERR_INVALID, "rabitq_search: workspace %zu < %zu bytes",
                  workspace_bytes, L.total);
@@ -597,7 +602,6 @@ extern "C" int mivq_rabitq_search(const uint8_t* codes, int64_t n, int32_t d, co
         hipError_t e = launch_topk_merge(nullptr, nullptr, 0, nq, k, dists, ids, st);
         return e == hipSuccess ? MIVQ_OK : set_error(MIVQ_ERR_HIP, "rabitq_search: %s", hipGetErrorString(e));
     }
-    const bool mfma = qb > 0 && (d % 32) == 0 && (reinterpret_cast<uintptr_t>(codes) % 4) == 0;
     // the multi-query kernel for d % 512 == 0 (32, 64 or 128 queries per workgroup by nq)
     const int nqb_mq = nq > 64 ? 4 : nq > 32 ? 2 : 1;
     const bool mq = mfma && (d % kEstKC) == 0;

@@ -37,6 +37,7 @@ MIVQ_PQ_LEGACY_EXACT = 4
 METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1
 NO_ID = 0xFFFFFFFF
+MAX_QUERIES_PER_CALL = 65535  # mivq_ivfpq_search, and mivq_rabitq_search on its generic estimator (grid.y)
 
 _c = ctypes
 _vp, _i32, _i64, _u32, _sz = _c.c_void_p, _c.c_int32, _c.c_int64, _c.c_uint32, _c.c_size_t
@@ -501,9 +502,16 @@ def rabitq_search(codes: torch.Tensor, d: int, centroid: Optional[torch.Tensor],
     n, nq = codes.shape[0], q.shape[0]
     dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
     ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
-    ws = workspace(load_library().mivq_rabitq_search_workspace_bytes(nq, n, d, k), q.device)
-    _call("mivq_rabitq_search", _ptr(codes), n, d, _ptr(centroid), _ptr(q), nq, qb, metric, k, id_offset, _ptr(ws),
-          ws.numel(), _ptr(dists), _ptr(ids), _stream())
+    # the generic estimator (qb = 0, d % 32 != 0 or unaligned codes) takes at most
+    # MAX_QUERIES_PER_CALL queries per call (its grid.y); queries are independent, so ranges of
+    # them give the rows of one call
+    generic = qb == 0 or d % 32 != 0 or codes.data_ptr() % 4 != 0
+    step = MAX_QUERIES_PER_CALL if generic else max(nq, 1)
+    for s in range(0, max(nq, 1), step):
+        c = min(nq, s + step) - s
+        ws = workspace(load_library().mivq_rabitq_search_workspace_bytes(c, n, d, k), q.device)
+        _call("mivq_rabitq_search", _ptr(codes), n, d, _ptr(centroid), _ptr(q[s:s + c]), c, qb, metric, k, id_offset,
+              _ptr(ws), ws.numel(), _ptr(dists[s:s + c]), _ptr(ids[s:s + c]), _stream())
     return dists, ids
 
 
@@ -813,13 +821,19 @@ def ivfpq_search(lut: torch.Tensor, probe_d: torch.Tensor, probe_l: torch.Tensor
     nq, M, _ = lut.shape
     nprobe = probe_l.shape[1]
     nlist = offsets.shape[0] - 1
+    if probe_d.shape != probe_l.shape or probe_l.shape[0] != nq:
+        raise ValueError("ivfpq_search: probe_d / probe_l must both be (nq, nprobe)")
     dists = torch.empty((nq, k), dtype=torch.float32, device=lut.device)
     ids = torch.empty((nq, k), dtype=torch.int32, device=lut.device)
-    nb = load_library().mivq_ivfpq_search_workspace_bytes(nq, nprobe, k)
-    ws = workspace(nb, lut.device)
-    _call("mivq_ivfpq_search", _ptr(lut), nq, M, nbits, _ptr(probe_d), _ptr(probe_l), nprobe, nlist, _ptr(offsets),
-          _ptr(list_codes), _ptr(list_ids), _ptr(tau), metric, k, _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids),
-          _stream())
+    # one call takes at most MAX_QUERIES_PER_CALL queries (the scan's grid.y); queries are
+    # independent, so ranges of them give the rows of one call
+    for s in range(0, max(nq, 1), MAX_QUERIES_PER_CALL):
+        c = min(nq, s + MAX_QUERIES_PER_CALL) - s
+        nb = load_library().mivq_ivfpq_search_workspace_bytes(c, nprobe, k)
+        ws = workspace(nb, lut.device)
+        _call("mivq_ivfpq_search", _ptr(lut[s:s + c]), c, M, nbits, _ptr(probe_d[s:s + c]), _ptr(probe_l[s:s + c]),
+              nprobe, nlist, _ptr(offsets), _ptr(list_codes), _ptr(list_ids), _ptr(tau), metric, k, _ptr(ws),
+              ws.numel(), _ptr(dists[s:s + c]), _ptr(ids[s:s + c]), _stream())
     return dists, ids
 
 
