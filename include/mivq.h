@@ -366,6 +366,74 @@ int mivq_ivf_rabitq_search(const float* q, int64_t nq, int32_t d, const float* c
                            void* workspace, size_t workspace_bytes, float* dists, uint32_t* ids,
                            void* stream);
 
+/* ------------------------------------------------------ IVF over per-list SQ / LVQ codes
+ * GPU counterpart of IvfQuantizedIndex (methods/search/ivf_quantized_index.py) for a
+ * ScalarQuantizer (4 / 8 / 16 bits, f32) or an LVQQuantizer (1..8 bits) per list, fitted on the
+ * list's residuals.  The parameters of all lists are (nlist, d) arrays; a row's are those of
+ * its list l = assign[i], its centroid c = coarse[l].  Every operation is fp32, one rounding
+ * per step:
+ *   residual   r_t = x_t - c_t
+ *   SQ fit     lo_l[t] = min, hi_l[t] = max over the list's rows of r_t (any order: exact),
+ *              den_l[t] = (hi - lo) + 1e-8f; an empty list: lo = 0, den = 1e-8f
+ *   LVQ fit    mu_l[t] = (f32 sum of r_t over the list's rows in ascending row order) /
+ *              (float)count, 0 for an empty list: mivq_ivf_residuals + mivq_centroid_update on a
+ *              zeroed output compute exactly this chain (no entry point of its own)
+ *   SQ row     the row mivq_sq_encode_f32 writes for r with (lo_l, den_l) (same layout, odd d
+ *              at 4 bits zero-padded)
+ *   LVQ row    the row mivq_lvq_encode writes for r with mu = mu_l: the quantised value is
+ *              (x - c) - mu_l, two roundings; the 8-byte trailer is unchanged
+ *   x^_t       dec_t + c_t, dec_t the float mivq_sq_decode_f32 / mivq_lvq_decode writes for the
+ *              row with its list's parameters (the decode entry points return x^)
+ *   key        L2: the sequential fmaf chain over t ascending of (q_t - x^_t)^2;
+ *              IP: -(fmaf chain of q_t * x^_t)                  (the chains of mivq_flat_search)
+ * assign[i] >= nlist is undefined behaviour (as for mivq_ivf_residuals).  offsets / order: the
+ * bucket sort of assign (mivq_bucket_sort). */
+int mivq_ivf_sq_fit(const float* x, int64_t n, int32_t d, const float* coarse, int32_t nlist,
+                    const int64_t* offsets, const uint32_t* order, float* lo, float* den,
+                    void* stream);
+int mivq_ivf_sq_encode(const float* x, int64_t n, int32_t d, const float* coarse, int32_t nlist,
+                       const uint32_t* assign, const float* lo, const float* den, int32_t nbits,
+                       void* codes, void* stream);
+int mivq_ivf_sq_decode(const void* codes, int64_t n, int32_t d, const float* coarse,
+                       int32_t nlist, const uint32_t* assign, const float* lo, const float* den,
+                       int32_t nbits, float* out, void* stream);
+int mivq_ivf_lvq_encode(const float* x, int64_t n, int32_t d, const float* coarse, int32_t nlist,
+                        const uint32_t* assign, const float* mu, int32_t nbits, uint8_t* codes,
+                        void* stream);
+int mivq_ivf_lvq_decode(const uint8_t* codes, int64_t n, int32_t d, const float* coarse,
+                        int32_t nlist, const uint32_t* assign, const float* mu, int32_t nbits,
+                        float* out, void* stream);
+/* Exact search over the probed lists.  probe_l (nq, nprobe): list ids; slots holding
+ * 0xFFFFFFFF, or any id >= nlist, are skipped; a query's slots name distinct lists.  offsets
+ * (nlist + 1) int64, list_codes (n, row bytes), list_ids (n,) in bucket order, lo / den / mu
+ * (nlist, d), all on the device.  dists/ids (nq, k): the k smallest (key, id) over the rows of
+ * the probed lists, ascending, id = the list_ids entry compared as uint32 (ids >= 2^31 rank
+ * after the smaller ones on equal keys); a NaN key ranks as +inf; padded with
+ * (+inf, 0xFFFFFFFF) after every real row.  The result does not depend on the order of a
+ * query's probe slots, and is bit-identical to decoding each probed list (the decode entry
+ * points above) and running mivq_flat_search over those rows.
+ * Limits, checked on the host before any launch (MIVQ_ERR_UNSUPPORTED): k in [1, 256]; nlist <=
+ * 16383; one query row plus the list's parameter rows and centroid (SQ 3, LVQ 2 rows of d
+ * rounded up to 4 floats) within 160 KiB of LDS.  nbits outside {4, 8, 16} / [1, 8], bad sizes
+ * and null pointers are MIVQ_ERR_INVALID.  Stream-ordered, no host synchronisation; the
+ * workspace size depends on the shape alone (queries are processed in chunks; at most 1 GiB)
+ * and is 0 for invalid or unsupported sizes. */
+size_t mivq_ivf_sq_search_workspace_bytes(int64_t nq, int64_t n, int32_t nlist, int32_t nprobe,
+                                          int32_t d, int32_t nbits, int32_t k);
+int mivq_ivf_sq_search(const float* q, int64_t nq, int32_t d, const float* coarse, int32_t nlist,
+                       const uint32_t* probe_l, int32_t nprobe, const int64_t* offsets,
+                       const void* list_codes, const uint32_t* list_ids, const float* lo,
+                       const float* den, int32_t nbits, int32_t metric, int32_t k,
+                       void* workspace, size_t workspace_bytes, float* dists, uint32_t* ids,
+                       void* stream);
+size_t mivq_ivf_lvq_search_workspace_bytes(int64_t nq, int64_t n, int32_t nlist, int32_t nprobe,
+                                           int32_t d, int32_t nbits, int32_t k);
+int mivq_ivf_lvq_search(const float* q, int64_t nq, int32_t d, const float* coarse, int32_t nlist,
+                        const uint32_t* probe_l, int32_t nprobe, const int64_t* offsets,
+                        const uint8_t* list_codes, const uint32_t* list_ids, const float* mu,
+                        int32_t nbits, int32_t metric, int32_t k, void* workspace,
+                        size_t workspace_bytes, float* dists, uint32_t* ids, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

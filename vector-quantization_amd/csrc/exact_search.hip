@@ -1,8 +1,8 @@
 // exact_search.hip — exact brute-force search on gfx950 over an f32 database
 // (mivq_flat_search, mivq_pairwise_distances) and over SQ-4/8/16, RaBitQ-1 and LVQ-1..8 codes.
 //
-// One distance chain, two paths, every row format.  A format (Fmt<>) says how a row's floats
-// are fetched; f32 is the format with no parameters and no dequantisation.  The packed codes
+// One distance chain, two paths, every row format.  A format (Fmt<>, code_internal.h) says how a
+// row's floats are fetched; f32 is the format with no parameters and no dequantisation.  The packed codes
 // are read once and dequantised in registers, so no fp32 copy of a coded database exists at
 // any point.  Every reconstruction x^_t is the float the decode kernels write (sq.hip
 // sq_decode_kernel, rabitq.hip rabitq_decode_kernel, lvq.hip lvq_decode_kernel; one rounding
@@ -29,154 +29,13 @@
 //
 // The choice between the two paths is flat_use_tiled(nq, n); both produce the same chains.
 #include "adc_internal.h"
+#include "code_internal.h"
 #include "topk.h"
 
 namespace mivq {
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// kLvq + B - 1 is LVQ with B bits per dimension, B = 1 .. 8; kF32 is the database itself
-enum : int { kSq4 = 0, kSq8 = 1, kSq16 = 2, kRbq = 3, kLvq = 4, kF32 = 12 };
-
-// Queries per scan workgroup: the queries and the `params` parameter rows of dp = d rounded up
-// to 4 floats share the LDS, within `lds_kib` at 8, 4 or 2 queries and 160 KiB at one.
-struct ScanPolicy {
-    int params;
-    int lds_kib;
-    bool narrow;  // no wider than the batch (search_layout)
-};
-
-// ---------------------------------------------------------------- row formats
-template <int FMT>
-struct Fmt {
-    static constexpr bool kIsLvq = FMT >= kLvq && FMT < kLvq + 8;
-    static constexpr int kB = kIsLvq ? FMT - kLvq + 1 : 0;  // LVQ bits per dimension
-    static constexpr uint32_t kMask = (1u << kB) - 1u;
-    // dims per 32-bit word of codes (LVQ: per unit of kB words)
-    static constexpr int kWordDims = FMT == kSq4 ? 8 : FMT == kSq8 ? 4 : FMT == kSq16 ? 2 : FMT == kF32 ? 1 : 32;
-    // words per wide load of the scan (16 B; 8 B for RaBitQ and LVQ, whose rows of d % 64 == 0
-    // are 8-B aligned: the 8-byte trailer follows a multiple of 8 code bytes)
-    static constexpr int kWideWords = FMT == kRbq || kIsLvq ? 2 : 4;
-    // per-dimension parameter arrays: SQ {den, lo}, RaBitQ {centroid}, LVQ {mu}, f32 none
-    static constexpr int kParams = FMT == kF32 ? 0 : FMT == kRbq || kIsLvq ? 1 : 2;
-    // The f32 scan keeps the launch policy it had as a kernel of its own: 96 KiB where the code
-    // formats take 128, and a query block that is not narrowed to the batch.  The difference is
-    // inherited, not measured: nobody has timed either format under the other's policy.
-    static constexpr ScanPolicy kPolicy = {kParams, FMT == kF32 ? 96 : 128, FMT != kF32};
-    static constexpr float kLevels = FMT == kSq4 ? 15.0f : FMT == kSq8 ? 255.0f : 65535.0f;
-    static constexpr float kRcpLevels = 1.0f / kLevels;  // RN(1 / L)
-
-    __host__ __device__ static int code_bytes(int d) {
-        if (kIsLvq) return (int)(((int64_t)d * kB + 7) / 8);
-        return FMT == kSq4 ? (d + 1) / 2 : FMT == kSq8 ? d : FMT == kSq16 ? 2 * d : FMT == kF32 ? 4 * d : (d + 7) / 8;
-    }
-    __host__ __device__ static int row_bytes(int d) { return code_bytes(d) + (FMT == kRbq || kIsLvq ? 8 : 0); }
-    // byte offset of dimension t (a multiple of kWordDims) in a row
-    __device__ static int byte_of(int t) {
-        return FMT == kSq4 ? t >> 1 : FMT == kSq8 ? t : FMT == kSq16 ? 2 * t : FMT == kF32 ? 4 * t : t >> 3;
-    }
-
-    // level (SQ) / sign bit (RaBitQ) / float bits (f32) of dimension u of the little-endian words w[]
-    template <int NW>
-    __device__ __forceinline__ static uint32_t level(const uint32_t (&w)[NW], int u) {
-        if (kIsLvq) {  // w[]: the unit's words byte-swapped, field u at bits [u kB, (u + 1) kB) from the top
-            const int o = u * kB, wi = o >> 5, end = (o & 31) + kB;
-            if (end <= 32) return (w[wi] >> (32 - end)) & kMask;
-            return ((w[wi] << (end - 32)) | (w[wi + 1 < NW ? wi + 1 : wi] >> (64 - end))) & kMask;
-        }
-        if (FMT == kF32) return w[u];
-        if (FMT == kSq8) return (w[u >> 2] >> (8 * (u & 3))) & 0xFFu;
-        if (FMT == kSq16) return (w[u >> 1] >> (16 * (u & 1))) & 0xFFFFu;
-        if (FMT == kSq4) {  // even dimension in the high nibble
-            const uint32_t b = (w[u >> 3] >> (8 * ((u >> 1) & 3))) & 0xFFu;
-            return (u & 1) ? (b & 0x0Fu) : (b >> 4);
-        }
-        return (w[u >> 5] >> (u & 31)) & 1u;
-    }
-    // the same for dimension t of row `cr`, one code element at a time
-    __device__ __forceinline__ static uint32_t level_at(const uint8_t* cr, int t) {
-        if (kIsLvq) {  // the field lies in two bytes at most (the byte after the last is the trailer's)
-            const int o = t * kB, fb = o >> 3;
-            const uint32_t v = (uint32_t)cr[fb] << 8 | cr[fb + 1];
-            return (v >> (16 - (o & 7) - kB)) & kMask;
-        }
-        if (FMT == kF32) return reinterpret_cast<const uint32_t*>(cr)[t];
-        if (FMT == kSq8) return cr[t];
-        if (FMT == kSq16) return reinterpret_cast<const uint16_t*>(cr)[t];
-        if (FMT == kSq4) {
-            const uint32_t b = cr[t >> 1];
-            return (t & 1) ? (b & 0x0Fu) : (b >> 4);
-        }
-        return (cr[t >> 3] >> (t & 7)) & 1u;
-    }
-    // x^_t.  SQ: a = den_t, b = lo_t, fadd(fmul(fdiv(level, L), den_t), lo_t) with the division as
-    // the reciprocal sequence of sq.hip's div_rn_rcp (RN(level / L) for every level 0 .. L).
-    // RaBitQ: a = c_t (0 without a centroid), p.x the row's fmul(fmul(fmul(0.5, mult), 2), 1/sqrt(d)).
-    // LVQ: a = mu_t, p = the row's {lo, delta}: fadd(fadd(lo, fmul(idx, delta)), mu_t).
-    // f32: the word is x_t.
-    __device__ __forceinline__ static float dequant(uint32_t lv, float a, float b, float2 p) {
-        if (FMT == kF32) return __uint_as_float(lv);
-        if (kIsLvq) return __fadd_rn(__fadd_rn(p.x, __fmul_rn((float)lv, p.y)), a);
-        if (FMT == kRbq) return __fadd_rn(lv ? p.x : -p.x, a);
-        const float f = (float)lv;
-        const float q0 = __fmul_rn(f, kRcpLevels);
-        const float e = __builtin_fmaf(-q0, kLevels, f);
-        const float s = __builtin_fmaf(e, kRcpLevels, q0);
-        return __fadd_rn(__fmul_rn(s, a), b);
-    }
-    // The row's own parameters from its trailer (read byte-wise: rows are unaligned).  RaBitQ: p
-    // in .x, from mult, the second trailer float; LVQ: {lo, delta}, the two trailer floats.
-    __device__ __forceinline__ static float2 row_scale(const uint8_t* cr, int d) {
-        if (FMT != kRbq && !kIsLvq) return make_float2(0.0f, 0.0f);
-        const int nb = code_bytes(d);
-        uint32_t u0 = 0, u1 = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (kIsLvq) u0 |= (uint32_t)cr[nb + q] << (8 * q);
-            u1 |= (uint32_t)cr[nb + 4 + q] << (8 * q);
-        }
-        if (kIsLvq) return make_float2(__uint_as_float(u0), __uint_as_float(u1));
-        const float inv_d_sqrt = __fdiv_rn(1.0f, sqrtf((float)d));
-        return make_float2(__fmul_rn(__fmul_rn(__fmul_rn(0.5f, __uint_as_float(u1)), 2.0f), inv_d_sqrt), 0.0f);
-    }
-};
-
-// ---------------------------------------------------------------- streaming scan
-// NW loaded words = NW * kWordDims (a multiple of 4) dimensions from t0 (a multiple of 4) on:
-// four at a time, the parameters and the queries as 16-B LDS reads.  LVQ: the kB byte-swapped
-// words of one unit, 32 dimensions.
-template <int FMT, int NW, int QB>
-__device__ __forceinline__ void scan_words(const uint32_t (&w)[NW], int t0, const float* qv, int dp, const float* pa,
-                                           const float* pb, float2 p, bool l2, float (&dist)[QB]) {
-    constexpr int ND = Fmt<FMT>::kIsLvq ? 32 : NW * Fmt<FMT>::kWordDims;
-    static_assert(ND % 4 == 0, "whole groups of four dimensions");
-#pragma unroll
-    for (int g = 0; g < ND; g += 4) {
-        float4 a4 = make_float4(0.f, 0.f, 0.f, 0.f), b4 = a4;
-        if constexpr (Fmt<FMT>::kParams >= 1) a4 = *reinterpret_cast<const float4*>(pa + t0 + g);
-        if constexpr (Fmt<FMT>::kParams == 2) b4 = *reinterpret_cast<const float4*>(pb + t0 + g);
-        const float x0 = Fmt<FMT>::dequant(Fmt<FMT>::level(w, g + 0), a4.x, b4.x, p);
-        const float x1 = Fmt<FMT>::dequant(Fmt<FMT>::level(w, g + 1), a4.y, b4.y, p);
-        const float x2 = Fmt<FMT>::dequant(Fmt<FMT>::level(w, g + 2), a4.z, b4.z, p);
-        const float x3 = Fmt<FMT>::dequant(Fmt<FMT>::level(w, g + 3), a4.w, b4.w, p);
-#pragma unroll
-        for (int qq = 0; qq < QB; ++qq) {
-            const float4 qf = *reinterpret_cast<const float4*>(qv + qq * dp + t0 + g);
-            if (l2) {
-                float df = __fsub_rn(qf.x, x0); dist[qq] = __builtin_fmaf(df, df, dist[qq]);
-                df = __fsub_rn(qf.y, x1); dist[qq] = __builtin_fmaf(df, df, dist[qq]);
-                df = __fsub_rn(qf.z, x2); dist[qq] = __builtin_fmaf(df, df, dist[qq]);
-                df = __fsub_rn(qf.w, x3); dist[qq] = __builtin_fmaf(df, df, dist[qq]);
-            } else {
-                dist[qq] = __builtin_fmaf(qf.x, x0, dist[qq]);
-                dist[qq] = __builtin_fmaf(qf.y, x1, dist[qq]);
-                dist[qq] = __builtin_fmaf(qf.z, x2, dist[qq]);
-                dist[qq] = __builtin_fmaf(qf.w, x3, dist[qq]);
-            }
-        }
-    }
-}
 
 // grid (nchunks, ceil(nq / QB)), block 1024.  LDS: [QB][dp] queries, then kParams x [dp]
 // parameters, dp = d rounded up to 4 (16-B aligned rows; the padding is never read).
@@ -217,75 +76,14 @@ __global__ __launch_bounds__(kScanWaves * 64) void code_scan_kernel(
     const int64_t rbeg = (int64_t)blockIdx.x * chunk_rows;
     const int64_t rend = min(n, rbeg + chunk_rows);
     const int64_t stride = F::row_bytes(d);
-    constexpr int NDW = F::kWideWords * F::kWordDims;
-    const int twide = wide ? d / NDW * NDW : 0;  // dimensions covered by whole wide loads
+    const ScanRows rows{qv, pa, pb, nullptr, dp};
     for (int64_t base = rbeg + (int64_t)wv * 64; base < rend; base += kScanWaves * 64) {
         const int64_t row = base + lane;
         const bool valid = row < rend;
         float dist[QB];
 #pragma unroll
         for (int qq = 0; qq < QB; ++qq) dist[qq] = 0.0f;
-        if (valid) {
-            const uint8_t* cr = codes + row * stride;
-            const float2 p = F::row_scale(cr, d);
-            int t = 0;
-            if constexpr (F::kIsLvq) {
-                // whole units of 32 dimensions = kB words: 8-B loads (even kB, 8-B aligned rows) or
-                // 4-B loads; the rest of the row, and every row of an unaligned database, below
-                constexpr int B = F::kB;
-                const int tunit = narrow ? d / 32 * 32 : 0;
-                for (; t < tunit; t += 32) {
-                    uint32_t w[B];
-                    const uint8_t* cu = cr + (t >> 3) * B;
-                    if (B % 2 == 0 && wide) {
-#pragma unroll
-                        for (int i = 0; i < B / 2; ++i) {
-                            const uint2 v = reinterpret_cast<const uint2*>(cu)[i];
-                            w[2 * i] = v.x;
-                            w[2 * i + (B > 1 ? 1 : 0)] = v.y;
-                        }
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < B; ++i) w[i] = reinterpret_cast<const uint32_t*>(cu)[i];
-                    }
-#pragma unroll
-                    for (int i = 0; i < B; ++i) w[i] = __builtin_bswap32(w[i]);
-                    scan_words<FMT, B, QB>(w, t, qv, dp, pa, pb, p, l2, dist);
-                }
-            } else {
-                for (; t < twide; t += NDW) {
-                    uint32_t w[F::kWideWords];
-                    if constexpr (F::kWideWords == 4) {
-                        const uint4 v = *reinterpret_cast<const uint4*>(cr + F::byte_of(t));
-                        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-                    } else {
-                        const uint2 v = *reinterpret_cast<const uint2*>(cr + F::byte_of(t));
-                        w[0] = v.x; w[1] = v.y;
-                    }
-                    scan_words<FMT, F::kWideWords, QB>(w, t, qv, dp, pa, pb, p, l2, dist);
-                }
-                if constexpr (F::kWordDims % 4 == 0) {  // (an SQ-16 word is half a group: no 4-B step)
-                    if (narrow) {
-                        for (; t + F::kWordDims <= d; t += F::kWordDims) {
-                            const uint32_t w[1] = {*reinterpret_cast<const uint32_t*>(cr + F::byte_of(t))};
-                            scan_words<FMT, 1, QB>(w, t, qv, dp, pa, pb, p, l2, dist);
-                        }
-                    }
-                }
-            }
-            for (; t < d; ++t) {
-                const float xh = F::dequant(F::level_at(cr, t), F::kParams >= 1 ? pa[t] : 0.0f, F::kParams == 2 ? pb[t] : 0.0f, p);
-#pragma unroll
-                for (int qq = 0; qq < QB; ++qq) {
-                    if (l2) {
-                        const float df = __fsub_rn(qv[qq * dp + t], xh);
-                        dist[qq] = __builtin_fmaf(df, df, dist[qq]);
-                    } else {
-                        dist[qq] = __builtin_fmaf(qv[qq * dp + t], xh, dist[qq]);
-                    }
-                }
-            }
-        }
+        if (valid) scan_row<FMT, QB, false>(codes + row * stride, d, rows, wide, narrow, l2, dist);
         const uint32_t gid = (uint32_t)(id_offset + row);
 #pragma unroll
         for (int qq = 0; qq < QB; ++qq) {
@@ -300,17 +98,6 @@ __global__ __launch_bounds__(kScanWaves * 64) void code_scan_kernel(
     for (int qq = 0; qq < QB; ++qq) {
         if (qq < nqb) top[qq].store(part_d + (part * nq + q0 + qq) * k, part_i + (part * nq + q0 + qq) * k, k, lane);
     }
-}
-
-// Queries per scan workgroup under policy P, before narrowing; 0: d does not fit the LDS.
-int scan_qb(int d, ScanPolicy P) {
-    const int64_t per = (int64_t)((d + 3) & ~3) * 4;
-    const int64_t budget = (int64_t)P.lds_kib * 1024;
-    if (per * (8 + P.params) <= budget) return 8;
-    if (per * (4 + P.params) <= budget) return 4;
-    if (per * (2 + P.params) <= budget) return 2;
-    if (per * (1 + P.params) <= 160 * 1024) return 1;
-    return 0;
 }
 
 template <int FMT, int R, int QB>

@@ -13,7 +13,7 @@
 //                           the pair's sort key (its list; skipped slots go to a bucket of their
 //                           own) and the sentinel fill of the pair's partial lists.
 //   mivq_bucket_sort        stable sort of the pairs by list: the pairs probing a list are contiguous.
-//   ivf_rabitq_items_kernel per-list pair counts -> work items (list, block of 32 pairs).
+//   ivf_items_kernel        per-list pair counts -> work items (list, block of 32 pairs); ivf_internal.h.
 //   ivf_rabitq_scan_kernel  grid (item bound, S code ranges): the integer dots of 32 pairs x 256
 //                           codes per step (v_mfma_i32_32x32x32_i8 when d % 32 == 0 and qb >= 1,
 //                           as rabitq_est_mfma_kernel; one thread per code otherwise), the
@@ -23,6 +23,7 @@
 //   topk_merge_kernel       merges the nprobe x S partial lists of every query.
 // List sizes live on the device: the grids are sized from the shape, the kernels find their work
 // from offsets and the item table.  Queries are processed in chunks so the workspace stays bounded.
+#include "ivf_internal.h"
 #include "mivq_common.h"
 #include "rabitq_internal.h"
 #include "topk.h"
@@ -76,37 +77,6 @@ __global__ __launch_bounds__(256) void ivf_rabitq_prep_kernel(const float* __res
     }
     if (!live) return;
     rabitq_qprep_row(q + a * d, d, coarse + (int64_t)l * d, qb, qq + p * d, nullptr, qf + p * kQfStride);
-}
-
-// poff: the bucket offsets of the sorted pairs (nlist + 2 entries; bucket nlist = skipped slots).
-// items[i] = (list, first sorted pair of the block), nitems = their count
-// (<= ceil(pairs / kIrPairs) + nlist).  One workgroup.
-__global__ __launch_bounds__(1024) void ivf_rabitq_items_kernel(const int64_t* __restrict__ poff, int nlist,
-                                                                uint2* __restrict__ items,
-                                                                uint32_t* __restrict__ nitems) {
-    __shared__ int64_t part[1024];
-    __shared__ int64_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nlist; base += 1024) {
-        const int l = base + threadIdx.x;
-        const int64_t p0 = l < nlist ? poff[l] : 0;
-        const int64_t v = l < nlist ? (poff[l + 1] - p0 + kIrPairs - 1) / kIrPairs : 0;
-        part[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {  // Hillis-Steele inclusive scan
-            const int64_t add = threadIdx.x >= o ? part[threadIdx.x - o] : 0;
-            __syncthreads();
-            part[threadIdx.x] += add;
-            __syncthreads();
-        }
-        const int64_t first = carry + part[threadIdx.x] - v;
-        for (int64_t b = 0; b < v; ++b) items[first + b] = make_uint2((uint32_t)l, (uint32_t)(p0 + b * kIrPairs));
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += part[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *nitems = (uint32_t)carry;
 }
 
 struct IrScan {
@@ -443,7 +413,7 @@ extern "C" int mivq_ivf_rabitq_search(const float* q, int64_t nq, int32_t d, con
         if (rc) return rc;
         rc = mivq_bucket_sort(keys, P, nlist + 1, poff, porder, p + L.sortws, L.pd - L.sortws, stream);
         if (rc) return rc;
-        hipLaunchKernelGGL(ivf_rabitq_items_kernel, dim3(1), dim3(1024), 0, st, poff, nlist, items, nitems);
+        hipLaunchKernelGGL(ivf_items_kernel<kIrPairs>, dim3(1), dim3(1024), 0, st, poff, nlist, items, nitems);
         rc = check_launch("ivf_rabitq_items");
         if (rc) return rc;
         const IrScan A{q + a0 * d, coarse, qq, qf, poff, porder, items, nitems, offsets, list_codes, list_ids,

@@ -17,226 +17,13 @@
 // so lane l owns the groups of 8 dimensions l, l + 64, ...: 32 contiguous bytes of x in, B
 // contiguous bytes out, no bits merged across lanes.  Up to d = 3072 (6 groups per lane) the
 // residuals stay in registers between the min/max pass and the quantisation, so x is read
-// once; beyond that the row is read a second time (from L2).
+// once; beyond that the row is read a second time (from L2).  The kernels are in
+// code_internal.h, shared with the per-list encode / decode of ivf_code.hip.
 #include <algorithm>
-#include <float.h>
-
-#include "mivq_common.h"
+#include "code_internal.h"
 
 namespace mivq {
 namespace {
-
-constexpr int kLvqMaxRegGroups = 6;  // groups of 8 dims a lane keeps in registers: d <= 3072
-
-// rint((r - lo) / delta) needs the correctly rounded quotient only where it can land on or next
-// to a tie.  With rcp = RN(1 / delta): q0 = RN(a rcp), the exact residual e = a - delta q0 (one
-// fma), q = RN(q0 + e rcp) is the correctly rounded a / delta (Markstein; sq.hip's div_rn_rcp)
-// as long as nothing over- or underflows.  A row takes this path when its delta lies in
-// [2^-60, 2^50]: then a = r - lo <= L delta < 2^58, and an a below 2^-62 is below delta / 4, where
-// any q near a / delta rounds to index 0.  Other rows (delta = FLT_MIN among them) divide in IEEE.
-__device__ __forceinline__ bool lvq_delta_ok(float delta) { return delta >= 0x1p-60f && delta <= 0x1p50f; }
-
-template <bool FAST>
-__device__ __forceinline__ float lvq_quotient(float a, float delta, float rcp) {
-    if (FAST) {
-        const float q0 = __fmul_rn(a, rcp);
-        const float e = __builtin_fmaf(-q0, delta, a);
-        return __builtin_fmaf(e, rcp, q0);
-    }
-    return __fdiv_rn(a, delta);
-}
-
-// v[u] = p[8 g + u], 0 beyond d (VEC: d % 4 == 0 and p 16-B aligned)
-template <bool VEC>
-__device__ __forceinline__ void lvq_load8(const float* __restrict__ p, int d, int g, float (&v)[8]) {
-    const int j0 = g * 8;
-    if (VEC && j0 + 8 <= d) {
-        const float4 a = *reinterpret_cast<const float4*>(p + j0), b = *reinterpret_cast<const float4*>(p + j0 + 4);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    } else {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = (j0 + u < d) ? p[j0 + u] : 0.0f;
-    }
-}
-
-__device__ __forceinline__ void lvq_minmax(const float (&r)[8], int d, int g, float& lo, float& hi) {
-    const int nv = min(8, d - g * 8);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        if (u < nv) {
-            lo = fminf(lo, r[u]);
-            hi = fmaxf(hi, r[u]);
-        }
-    }
-}
-
-// Quantises group g and writes its bytes: B of them, fewer for the ragged last group.  `sw`:
-// every group start of every row is aligned for stores of that many bytes (8, 4, 2 or 1), and
-// B is a multiple of it.
-template <bool FAST>
-__device__ __forceinline__ void lvq_emit(const float (&r)[8], int d, int g, float lo, float delta, float rcp, int B,
-                                         int ib, int sw, uint8_t* __restrict__ code) {
-    const float Lf = (float)((1 << B) - 1);
-    const int nv = min(8, d - g * 8);
-    uint32_t half[2] = {0u, 0u};  // four indices each: 4 B <= 32 bits
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const float q = lvq_quotient<FAST>(__fsub_rn(r[u], lo), delta, rcp);
-        // clipped before the cast (NaN -> 0): the index is always in [0, L]
-        const uint32_t idx = u < nv ? (uint32_t)fminf(fmaxf(rintf(q), 0.0f), Lf) : 0u;
-        half[u >> 2] = (half[u >> 2] << B) | idx;
-    }
-    const uint64_t acc = ((uint64_t)half[0] << (4 * B)) | half[1];
-    // the group's big-endian image, left-aligned, as the little-endian word that stores it
-    const uint64_t w = __builtin_bswap64(acc << (64 - 8 * B));
-    const int nbytes = min(B, ib - g * B);
-    uint8_t* p = code + (int64_t)g * B;
-    if (nbytes == B && sw == 8) {
-        *reinterpret_cast<uint2*>(p) = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
-    } else if (nbytes == B && sw == 4) {
-        *reinterpret_cast<uint32_t*>(p) = (uint32_t)w;
-        if (B == 8) *reinterpret_cast<uint32_t*>(p + 4) = (uint32_t)(w >> 32);
-    } else if (nbytes == B && sw == 2) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (2 * k < B) *reinterpret_cast<uint16_t*>(p + 2 * k) = (uint16_t)(w >> (16 * k));
-    } else {
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (k < nbytes) p[k] = (uint8_t)(w >> (8 * k));
-    }
-}
-
-// 4 rows (waves) per workgroup, grid-stride over rows.  G > 0: the lane's G groups in registers
-// (64 * 8 * G >= d), and its part of mu too, loaded once for all the rows the wave walks; G == 0:
-// any d, the row (and mu) read twice.
-template <int G, bool VEC>
-__global__ __launch_bounds__(256) void lvq_encode_kernel(const float* __restrict__ x, int64_t n, int d,
-                                                         const float* __restrict__ mu, int B, int sw,
-                                                         uint8_t* __restrict__ codes) {
-    const int lane = threadIdx.x & 63;
-    const int groups = (d + 7) >> 3;
-    const int ib = (int)(((int64_t)d * B + 7) >> 3);
-    const int64_t cs = (int64_t)ib + 8;
-    const float Lf = (float)((1 << B) - 1);
-    float m[G > 0 ? G : 1][8];
-    if constexpr (G > 0) {
-#pragma unroll
-        for (int i = 0; i < G; ++i)
-            if (lane + 64 * i < groups) lvq_load8<VEC>(mu, d, lane + 64 * i, m[i]);
-    }
-    for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += (int64_t)gridDim.x * 4) {
-        const float* xr = x + row * d;
-        uint8_t* code = codes + row * cs;
-        float lo = INFINITY, hi = -INFINITY;
-        float r[G > 0 ? G : 1][8];
-        if constexpr (G > 0) {
-#pragma unroll
-            for (int i = 0; i < G; ++i)
-                if (lane + 64 * i < groups) lvq_load8<VEC>(xr, d, lane + 64 * i, r[i]);
-#pragma unroll
-            for (int i = 0; i < G; ++i) {
-                if (lane + 64 * i < groups) {
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) r[i][u] = __fsub_rn(r[i][u], m[i][u]);
-                    lvq_minmax(r[i], d, lane + 64 * i, lo, hi);
-                }
-            }
-        } else {
-            for (int g = lane; g < groups; g += 64) {
-                lvq_load8<VEC>(xr, d, g, r[0]);
-                lvq_load8<VEC>(mu, d, g, m[0]);
-#pragma unroll
-                for (int u = 0; u < 8; ++u) r[0][u] = __fsub_rn(r[0][u], m[0][u]);
-                lvq_minmax(r[0], d, g, lo, hi);
-            }
-        }
-        lo = wave_min(lo);
-        hi = wave_max(hi);
-        const float span = __fsub_rn(hi, lo);
-        const float delta = span == 0.0f ? FLT_MIN : __fdiv_rn(span, Lf);
-        const float rcp = __fdiv_rn(1.0f, delta);
-        const bool fast = lvq_delta_ok(delta);  // the same in every lane
-        if constexpr (G > 0) {
-#pragma unroll
-            for (int i = 0; i < G; ++i) {
-                const int g = lane + 64 * i;
-                if (g < groups) {
-                    if (fast) lvq_emit<true>(r[i], d, g, lo, delta, rcp, B, ib, sw, code);
-                    else lvq_emit<false>(r[i], d, g, lo, delta, rcp, B, ib, sw, code);
-                }
-            }
-        } else {
-            for (int g = lane; g < groups; g += 64) {
-                lvq_load8<VEC>(xr, d, g, r[0]);
-                lvq_load8<VEC>(mu, d, g, m[0]);
-#pragma unroll
-                for (int u = 0; u < 8; ++u) r[0][u] = __fsub_rn(r[0][u], m[0][u]);
-                if (fast) lvq_emit<true>(r[0], d, g, lo, delta, rcp, B, ib, sw, code);
-                else lvq_emit<false>(r[0], d, g, lo, delta, rcp, B, ib, sw, code);
-            }
-        }
-        if (lane == 0) {  // the trailer sits at any byte offset
-            const uint32_t u0 = __float_as_uint(lo), u1 = __float_as_uint(delta);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                code[ib + q] = (uint8_t)(u0 >> (8 * q));
-                code[ib + 4 + q] = (uint8_t)(u1 >> (8 * q));
-            }
-        }
-    }
-}
-
-// One lane per group of 8 dimensions: its B bytes and the row's trailer byte-wise in, two
-// 16-B stores out (VEC: d % 4 == 0, mu and out 16-B aligned).
-template <bool VEC>
-__global__ __launch_bounds__(256) void lvq_decode_kernel(const uint8_t* __restrict__ codes, int64_t n, int d,
-                                                         const float* __restrict__ mu, int B, float* __restrict__ out) {
-    const int groups = (d + 7) >> 3;
-    const int ib = (int)(((int64_t)d * B + 7) >> 3);
-    const int64_t cs = (int64_t)ib + 8;
-    const uint32_t L = (1u << B) - 1u;
-    const int64_t total = n * groups;
-    for (int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x; gid < total; gid += (int64_t)gridDim.x * 256) {
-        const int64_t i = gid / groups;
-        const int g = (int)(gid - i * groups);
-        const int j0 = g * 8;
-        const uint8_t* code = codes + i * cs;
-        const int nbytes = min(B, ib - g * B);
-        uint64_t v = 0;  // the group's bits, left-aligned
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (k < nbytes) v |= (uint64_t)code[(int64_t)g * B + k] << (56 - 8 * k);
-        uint32_t u0 = 0, u1 = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            u0 |= (uint32_t)code[ib + q] << (8 * q);
-            u1 |= (uint32_t)code[ib + 4 + q] << (8 * q);
-        }
-        const float lo = __uint_as_float(u0), delta = __uint_as_float(u1);
-        float o[8];
-        float* orow = out + i * d + j0;
-        if (VEC && j0 + 8 <= d) {
-            const float4 ma = *reinterpret_cast<const float4*>(mu + j0), mb = *reinterpret_cast<const float4*>(mu + j0 + 4);
-            const float mv[8] = {ma.x, ma.y, ma.z, ma.w, mb.x, mb.y, mb.z, mb.w};
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const uint32_t idx = (uint32_t)(v >> (64 - B * (u + 1))) & L;
-                o[u] = __fadd_rn(__fadd_rn(lo, __fmul_rn((float)idx, delta)), mv[u]);
-            }
-            reinterpret_cast<float4*>(orow)[0] = make_float4(o[0], o[1], o[2], o[3]);
-            reinterpret_cast<float4*>(orow)[1] = make_float4(o[4], o[5], o[6], o[7]);
-        } else {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (j0 + u < d) {
-                    const uint32_t idx = (uint32_t)(v >> (64 - B * (u + 1))) & L;
-                    orow[u] = __fadd_rn(__fadd_rn(lo, __fmul_rn((float)idx, delta)), mu[j0 + u]);
-                }
-            }
-        }
-    }
-}
 
 // mean_c = (fp32 sum of column c in ascending row order) / (float)n, what numpy's
 // X.mean(axis=0) computes for a C-contiguous f32 array.  A workgroup owns kCmCols columns:
@@ -307,7 +94,7 @@ void launch_lvq_encode(const float* x, int64_t n, int d, const float* mu, int B,
     // (and grid.x stays far below its limit for any n)
     const dim3 grid((unsigned)std::min<int64_t>(ceil_div(n, 4), (int64_t)device_cus() * 32));
 #define MIVQ_LVQ_ENC(G) \
-    hipLaunchKernelGGL((lvq_encode_kernel<G, VEC>), grid, dim3(256), 0, st, x, n, d, mu, B, sw, codes)
+    hipLaunchKernelGGL((lvq_encode_kernel<G, VEC, false>), grid, dim3(256), 0, st, x, n, d, nullptr, nullptr, mu, B, sw, codes)
     if (per_lane <= 1) MIVQ_LVQ_ENC(1);
     else if (per_lane == 2) MIVQ_LVQ_ENC(2);
     else if (per_lane == 3) MIVQ_LVQ_ENC(3);
@@ -362,8 +149,8 @@ extern "C" int mivq_lvq_decode(const uint8_t* codes, int64_t n, int32_t d, const
     MIVQ_REQUIRE(codes && mu && out, MIVQ_ERR_INVALID, "lvq_decode: null pointer");
     const dim3 grid((unsigned)std::min<int64_t>(ceil_div(n * (int64_t)((d + 7) / 8), 256), 1 << 24));
     if (d % 4 == 0 && aligned16(mu) && aligned16(out))
-        hipLaunchKernelGGL(lvq_decode_kernel<true>, grid, dim3(256), 0, as_stream(stream), codes, n, d, mu, nbits, out);
+        hipLaunchKernelGGL((lvq_decode_kernel<true, false>), grid, dim3(256), 0, as_stream(stream), codes, n, d, nullptr, nullptr, mu, nbits, out);
     else
-        hipLaunchKernelGGL(lvq_decode_kernel<false>, grid, dim3(256), 0, as_stream(stream), codes, n, d, mu, nbits, out);
+        hipLaunchKernelGGL((lvq_decode_kernel<false, false>), grid, dim3(256), 0, as_stream(stream), codes, n, d, nullptr, nullptr, mu, nbits, out);
     return check_launch("lvq_decode");
 }

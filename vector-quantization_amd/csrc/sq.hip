@@ -9,30 +9,14 @@
 // (NaN, +-inf, |r| >= 2^31) -> 0.
 //
 // Layout: one lane handles 8 consecutive dims of a row (HBM-bound; vector loads and packed
-// stores on the aligned f32 fast path).
+// stores on the aligned f32 fast path).  The generic kernels (any d, any alignment, f64) are in
+// code_internal.h, shared with the per-list encode / decode of ivf_code.hip.
 #include <algorithm>
 
-#include "mivq_common.h"
+#include "code_internal.h"
 
 namespace mivq {
 namespace {
-
-template <typename T>
-__device__ __forceinline__ uint32_t np_cast_uint(T r) {
-    if (!(r >= (T)-2147483648.0 && r < (T)2147483648.0)) return 0u;
-    return (uint32_t)(int32_t)r;
-}
-
-__device__ __forceinline__ float sq_step(float x, float lo, float den, float L) {
-    const float a = __fsub_rn(x, lo);
-    const float b = __fdiv_rn(a, den);
-    return rintf(__fmul_rn(b, L));
-}
-__device__ __forceinline__ double sq_step(double x, double lo, double den, double L) {
-    const double a = __dsub_rn(x, lo);
-    const double b = __ddiv_rn(a, den);
-    return rint(__dmul_rn(b, L));
-}
 
 // RN(a / den) from rcp = RN(1 / den) (vector fast path): q0 = RN(a rcp), the exact residual
 // e = a - den q0 (one fma), q = RN(q0 + e rcp).  With rcp correctly rounded and q0 within an ulp
@@ -47,39 +31,6 @@ __device__ __forceinline__ float div_rn_rcp(float a, float den, float rcp, bool 
         return __builtin_fmaf(e, rcp, q0);
     }
     return __fdiv_rn(a, den);
-}
-
-// Each thread: row i, dims [8g, 8g+8).  Output written as bytes / u16.
-template <typename T>
-__global__ void sq_encode_kernel(const T* __restrict__ x, int64_t n, int d, const T* __restrict__ lo,
-                                 const T* __restrict__ den, int nbits, void* __restrict__ codes) {
-    const int groups = (d + 7) / 8;
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= n * groups) return;
-    const int64_t i = gid / groups;
-    const int j0 = (int)(gid % groups) * 8;
-    const T L = (T)((1 << nbits) - 1);
-    uint32_t q[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int j = j0 + u;
-        q[u] = j < d ? np_cast_uint(sq_step(x[i * d + j], lo[j], den[j], L)) : 0u;
-    }
-    if (nbits == 8) {
-        uint8_t* o = static_cast<uint8_t*>(codes) + i * d + j0;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) if (j0 + u < d) o[u] = (uint8_t)q[u];
-    } else if (nbits == 16) {
-        uint16_t* o = static_cast<uint16_t*>(codes) + i * d + j0;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) if (j0 + u < d) o[u] = (uint16_t)q[u];
-    } else {  // 4-bit: (q[:,0::2] << 4) | q[:,1::2] in uint8 arithmetic, odd d zero-padded
-        const int cw = (d + 1) / 2;
-        uint8_t* o = static_cast<uint8_t*>(codes) + i * cw + j0 / 2;
-#pragma unroll
-        for (int u = 0; u < 8; u += 2)
-            if ((j0 + u) / 2 < cw) o[u / 2] = (uint8_t)(((uint8_t)q[u] << 4) | (uint8_t)q[u + 1]);
-    }
 }
 
 // Fast path (f32, d % 8 == 0, 16-B aligned rows): column-stationary.  Block (gx, gy) covers
@@ -160,29 +111,6 @@ __global__ __launch_bounds__(256) void sq_encode_f32_vec_kernel(const float* __r
     }
 }
 
-__device__ __forceinline__ float sq_level(const void* codes, int64_t i, int j, int d, int nbits) {
-    if (nbits == 16) return (float)static_cast<const uint16_t*>(codes)[i * d + j];
-    if (nbits == 8) return (float)static_cast<const uint8_t*>(codes)[i * d + j];
-    const uint8_t b = static_cast<const uint8_t*>(codes)[i * ((d + 1) / 2) + (j >> 1)];
-    return (float)((j & 1) ? (b & 0x0F) : (b >> 4));
-}
-
-template <typename T>
-__global__ void sq_decode_kernel(const void* __restrict__ codes, int64_t n, int d, const T* __restrict__ lo,
-                                 const T* __restrict__ den, int nbits, T* __restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n * (int64_t)d) return;
-    const int64_t i = e / d;
-    const int j = (int)(e % d);
-    const float L = (float)((1 << nbits) - 1);
-    const float s = __fdiv_rn(sq_level(codes, i, j, d, nbits), L);
-    if constexpr (sizeof(T) == 4) {
-        out[e] = __fadd_rn(__fmul_rn(s, den[j]), lo[j]);
-    } else {
-        out[e] = __dadd_rn(__dmul_rn((double)s, den[j]), lo[j]);
-    }
-}
-
 // Fast decode path (f32 out, d % 8 == 0, aligned): one lane per 8 dims, packed code load, two
 // 16-B stores.
 __global__ void sq_decode_f32_vec_kernel(const void* __restrict__ codes, int64_t n, int d, const float* __restrict__ lo,
@@ -241,8 +169,8 @@ int sq_encode(const T* x, int64_t n, int32_t d, const T* lo, const T* den, int32
             return check_launch(name);
         }
     }
-    hipLaunchKernelGGL(sq_encode_kernel<T>, dim3((unsigned)ceil_div(work, 256)), dim3(256), 0, as_stream(stream),
-                       x, n, d, lo, den, nbits, codes);
+    hipLaunchKernelGGL((sq_encode_kernel<T, false>), dim3((unsigned)ceil_div(work, 256)), dim3(256), 0, as_stream(stream),
+                       x, n, d, (const T*)nullptr, (const uint32_t*)nullptr, lo, den, nbits, codes);
     return check_launch(name);
 }
 
@@ -263,8 +191,8 @@ int sq_decode(const void* codes, int64_t n, int32_t d, const T* lo, const T* den
             return check_launch(name);
         }
     }
-    hipLaunchKernelGGL(sq_decode_kernel<T>, dim3((unsigned)ceil_div(n * (int64_t)d, 256)), dim3(256), 0,
-                       as_stream(stream), codes, n, d, lo, den, nbits, out);
+    hipLaunchKernelGGL((sq_decode_kernel<T, false>), dim3((unsigned)ceil_div(n * (int64_t)d, 256)), dim3(256), 0,
+                       as_stream(stream), codes, n, d, (const T*)nullptr, (const uint32_t*)nullptr, lo, den, nbits, out);
     return check_launch(name);
 }
 

@@ -108,6 +108,17 @@ SIGNATURES = {
     "mivq_ivf_rabitq_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32, _i32]),
     "mivq_ivf_rabitq_search": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32,
                                           _vp, _sz, _vp, _vp, _vp]),
+    "mivq_ivf_sq_fit": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mivq_ivf_sq_encode": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "mivq_ivf_sq_decode": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "mivq_ivf_lvq_encode": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "mivq_ivf_lvq_decode": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "mivq_ivf_sq_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32, _i32, _i32]),
+    "mivq_ivf_sq_search": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
+                                      _vp, _sz, _vp, _vp, _vp]),
+    "mivq_ivf_lvq_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32, _i32, _i32]),
+    "mivq_ivf_lvq_search": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
+                                       _vp, _sz, _vp, _vp, _vp]),
 }
 
 ABI_VERSION = 2  # MIVQ_ABI_VERSION of include/mivq.h the table above binds
@@ -883,4 +894,146 @@ def ivf_rabitq_search(q: torch.Tensor, coarse: torch.Tensor, probe_l: torch.Tens
     ws = workspace(load_library().mivq_ivf_rabitq_search_workspace_bytes(nq, n, nlist, nprobe, d, k), q.device)
     _call("mivq_ivf_rabitq_search", _ptr(q), nq, d, _ptr(coarse), nlist, _ptr(probe_l), nprobe, _ptr(offsets),
           _ptr(list_codes), _ptr(list_ids), qb, metric, k, _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids), _stream())
+    return dists, ids
+
+
+# ----------------------------------------------------------------- IVF over per-list SQ / LVQ codes
+def sq_code_width(d: int, nbits: int) -> int:
+    """Elements per SQ code row (uint8; int16 at 16 bits)."""
+    if nbits not in (4, 8, 16):
+        raise ValueError(f"num_bits must be 4, 8, or 16, got {nbits}")
+    return (d + 1) // 2 if nbits == 4 else d
+
+
+def _ivf_code_check(coarse: torch.Tensor, assign: Optional[torch.Tensor], params, n: int, d: int, what: str) -> None:
+    _check(coarse, "coarse", torch.float32, 2)
+    if assign is not None:
+        _check(assign, "assign", torch.int32, 1)
+    if coarse.shape[1] != d or (assign is not None and assign.shape[0] != n):
+        raise ValueError(f"{what}: shape mismatch")
+    for name, t in params:
+        _check(t, name, torch.float32, 2)
+        if tuple(t.shape) != tuple(coarse.shape):
+            raise ValueError(f"{what}: {name} is {tuple(t.shape)}, expected {tuple(coarse.shape)}")
+
+
+def ivf_sq_fit(x: torch.Tensor, coarse: torch.Tensor, offsets: torch.Tensor,
+               order: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(lo, den) (nlist, d) of the per-list scalar quantizers: min and (max - min) + 1e-8 of the
+    residuals x - coarse[list] over each list's rows (offsets / order: bucket_sort of the lists)."""
+    _check(x, "x", torch.float32, 2)
+    _check(coarse, "coarse", torch.float32, 2)
+    _check(offsets, "offsets", torch.int64, 1)
+    _check(order, "order", torch.int32, 1)
+    n, d = x.shape
+    nlist = coarse.shape[0]
+    if coarse.shape[1] != d or offsets.shape[0] != nlist + 1 or order.shape[0] != n:
+        raise ValueError("ivf_sq_fit: shape mismatch")
+    lo = torch.empty_like(coarse)
+    den = torch.empty_like(coarse)
+    _call("mivq_ivf_sq_fit", _ptr(x), n, d, _ptr(coarse), nlist, _ptr(offsets), _ptr(order), _ptr(lo), _ptr(den),
+          _stream())
+    return lo, den
+
+
+def ivf_sq_encode(x: torch.Tensor, coarse: torch.Tensor, assign: torch.Tensor, lo: torch.Tensor, den: torch.Tensor,
+                  nbits: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """SQ code rows of x - coarse[assign[i]] with row assign[i] of lo / den; bit-identical to
+    sq_encode(residual, lo[l], den[l]).  assign values >= nlist are undefined."""
+    _check(x, "x", torch.float32, 2)
+    n, d = x.shape
+    _ivf_code_check(coarse, assign, (("lo", lo), ("den", den)), n, d, "ivf_sq_encode")
+    shape = (n, sq_code_width(d, nbits))
+    dt = torch.int16 if nbits == 16 else torch.uint8
+    if out is None:
+        out = torch.empty(shape, dtype=dt, device=x.device)
+    else:
+        _check(out, "out", dt, 2)
+        if tuple(out.shape) != shape:
+            raise ValueError("ivf_sq_encode: out has the wrong shape")
+    _call("mivq_ivf_sq_encode", _ptr(x), n, d, _ptr(coarse), coarse.shape[0], _ptr(assign), _ptr(lo), _ptr(den), nbits,
+          _ptr(out), _stream())
+    return out
+
+
+def ivf_sq_decode(codes: torch.Tensor, coarse: torch.Tensor, assign: torch.Tensor, lo: torch.Tensor,
+                  den: torch.Tensor, nbits: int) -> torch.Tensor:
+    """x^ (n, d) f32: sq_decode(row, lo[l], den[l]) + coarse[l], l = assign[i]."""
+    d = coarse.shape[1]
+    _sq_code_check(codes, d, nbits, "ivf_sq_decode")
+    n = codes.shape[0]
+    _ivf_code_check(coarse, assign, (("lo", lo), ("den", den)), n, d, "ivf_sq_decode")
+    out = torch.empty((n, d), dtype=torch.float32, device=codes.device)
+    _call("mivq_ivf_sq_decode", _ptr(codes), n, d, _ptr(coarse), coarse.shape[0], _ptr(assign), _ptr(lo), _ptr(den),
+          nbits, _ptr(out), _stream())
+    return out
+
+
+def ivf_lvq_encode(x: torch.Tensor, coarse: torch.Tensor, assign: torch.Tensor, mu: torch.Tensor, nbits: int,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LVQ code rows of x - coarse[assign[i]] with mu = row assign[i] of mu (nlist, d); bit-identical
+    to lvq_encode(residual, mu[l]).  assign values >= nlist are undefined."""
+    _lvq_bits_check(nbits)
+    _check(x, "x", torch.float32, 2)
+    n, d = x.shape
+    _ivf_code_check(coarse, assign, (("mu", mu),), n, d, "ivf_lvq_encode")
+    shape = (n, lvq_code_size(d, nbits))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    else:
+        _check(out, "out", torch.uint8, 2)
+        if tuple(out.shape) != shape:
+            raise ValueError("ivf_lvq_encode: out has the wrong shape")
+    _call("mivq_ivf_lvq_encode", _ptr(x), n, d, _ptr(coarse), coarse.shape[0], _ptr(assign), _ptr(mu), nbits, _ptr(out),
+          _stream())
+    return out
+
+
+def ivf_lvq_decode(codes: torch.Tensor, coarse: torch.Tensor, assign: torch.Tensor, mu: torch.Tensor,
+                   nbits: int) -> torch.Tensor:
+    """x^ (n, d) f32: lvq_decode(row, mu[l]) + coarse[l], l = assign[i]."""
+    d = coarse.shape[1]
+    _lvq_code_check(codes, d, nbits, "ivf_lvq_decode")
+    n = codes.shape[0]
+    _ivf_code_check(coarse, assign, (("mu", mu),), n, d, "ivf_lvq_decode")
+    out = torch.empty((n, d), dtype=torch.float32, device=codes.device)
+    _call("mivq_ivf_lvq_decode", _ptr(codes), n, d, _ptr(coarse), coarse.shape[0], _ptr(assign), _ptr(mu), nbits,
+          _ptr(out), _stream())
+    return out
+
+
+def ivf_code_search(kind: str, q: torch.Tensor, coarse: torch.Tensor, probe_l: torch.Tensor, offsets: torch.Tensor,
+                    list_codes: torch.Tensor, list_ids: torch.Tensor, params: Tuple[torch.Tensor, ...], nbits: int,
+                    metric: int, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact search over the probed lists of per-list SQ (kind 'sq', params (lo, den)) or LVQ
+    (kind 'lvq', params (mu,)) codes: (keys f32 (nq, k), ids int32 (nq, k) holding uint32 ids),
+    ascending; IP keys are negated inner products; missing slots hold (+inf, 0xFFFFFFFF)."""
+    if kind not in ("sq", "lvq"):
+        raise ValueError(f"ivf_code_search: kind must be 'sq' or 'lvq', got {kind!r}")
+    _check(q, "q", torch.float32, 2)
+    _check(probe_l, "probe_l", torch.int32, 2)
+    _check(offsets, "offsets", torch.int64, 1)
+    _check(list_ids, "list_ids", torch.int32, 1)
+    nq, d = q.shape
+    if kind == "sq":
+        _sq_code_check(list_codes, d, nbits, "ivf_code_search")
+        names = ("lo", "den")
+    else:
+        _lvq_code_check(list_codes, d, nbits, "ivf_code_search")
+        names = ("mu",)
+    if len(params) != len(names):
+        raise ValueError(f"ivf_code_search: {kind} takes the parameters {names}")
+    n = list_codes.shape[0]
+    nlist, nprobe = coarse.shape[0], probe_l.shape[1]
+    _ivf_code_check(coarse, None, tuple(zip(names, params)), n, d, "ivf_code_search")
+    if probe_l.shape[0] != nq or offsets.shape[0] != nlist + 1 or list_ids.shape[0] != n:
+        raise ValueError("ivf_code_search: shape mismatch")
+    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+    lib = load_library()
+    size_fn = lib.mivq_ivf_sq_search_workspace_bytes if kind == "sq" else lib.mivq_ivf_lvq_search_workspace_bytes
+    ws = workspace(size_fn(nq, n, nlist, nprobe, d, nbits, k), q.device)
+    _call(f"mivq_ivf_{kind}_search", _ptr(q), nq, d, _ptr(coarse), nlist, _ptr(probe_l), nprobe, _ptr(offsets),
+          _ptr(list_codes), _ptr(list_ids), *[_ptr(t) for t in params], nbits, metric, k, _ptr(ws), ws.numel(),
+          _ptr(dists), _ptr(ids), _stream())
     return dists, ids

@@ -3,4 +3,13 @@
 from .base_quantizer import BaseQuantizer
 from .base_search_index import BaseSearchIndex
 
-__all__ = ["BaseQuantizer", "BaseSearchIndex"]
+__all__ = ["BaseQuantizer", "BaseSearchIndex", "IvfQuantizedIndex"]
+
+
+def __getattr__(name):
+    # resolved on first use: the search indexes import torch and the native library
+    if name == "IvfQuantizedIndex":
+        from .search.ivf_quantized_index import IvfQuantizedIndex
+
+        return IvfQuantizedIndex
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

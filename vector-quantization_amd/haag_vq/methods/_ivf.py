@@ -18,6 +18,9 @@ of benchmarks/ivf_benchmark.py:170-204:
 * ``IvfRaBitQ``  RaBitQ-1 codes of x - coarse[list(x)] (faiss ``IVF{nlist},RaBitQ``): the encode
   whose centre is the row's list centroid, lists in bucket order, and the estimator search over
   the probed lists with the query residual re-quantised per (query, list) pair.
+* ``IvfCodes``  per-list SQ / LVQ codes of x - coarse[list(x)] (the reference's IvfQuantizedIndex:
+  one quantizer per list, fitted on the list's residuals): the parameters of all lists as
+  (nlist, d) tensors, lists in bucket order, and the exact search over the probed lists.
 
 faiss itself is absent here, so coarse centroids, codebooks and results are not claimed to
 equal faiss'; the arithmetic is the canonical one of include/mivq.h and oracle/.
@@ -255,3 +258,114 @@ class IvfRaBitQ:
         _, pl = _native.topk_rows(_native.pairwise_distances(Q, self.coarse, self.metric), nprobe)
         L = self.lists
         return _native.ivf_rabitq_search(Q, self.coarse, pl, L.offsets, L.codes, L.ids, qb, self.metric, k)
+
+
+class IvfCodes:
+    """IVF over per-list SQ ('sq': 4 / 8 / 16 bits) or LVQ ('lvq': 1..8 bits) codes of the residuals
+    (device-resident); the engine behind IvfQuantizedIndex.  ``params`` are (nlist, d) f32 tensors:
+    (lo, den) for SQ, (mu,) for LVQ; ``pos[id]`` is the bucket position of row ``id``."""
+
+    def __init__(self, d: int, K: int, kind: str, nbits: int, metric: int = _native.METRIC_L2) -> None:
+        if kind not in ("sq", "lvq"):
+            raise ValueError(f"kind must be 'sq' or 'lvq', got {kind!r}")
+        self.d, self.K, self.kind, self.nbits, self.metric = d, K, kind, int(nbits), metric
+        self.coarse: Optional[torch.Tensor] = None
+        self.params: Optional[Tuple[torch.Tensor, ...]] = None
+        self.lists: Optional[IvfLists] = None
+        self.pos: Optional[torch.Tensor] = None
+        self.ntotal = 0
+
+    def train(self, X: torch.Tensor, coarse_iters: int = 10, seed: int = 1234) -> None:
+        self.coarse = train_coarse(X, self.K, niter=coarse_iters, seed=seed, metric=self.metric)
+
+    def _assign(self, X: torch.Tensor) -> torch.Tensor:
+        n = X.shape[0]
+        a = torch.empty(n, dtype=torch.int32, device=X.device)
+        step = _rows_per_chunk(self.K)
+        for s in range(0, n, step):
+            e = min(n, s + step)
+            _, a[s:e] = assign(X[s:e], self.coarse, self.metric)
+        return a
+
+    def _lvq_means(self, X: torch.Tensor, a: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor) -> torch.Tensor:
+        """mu (K, d): the ascending-row f32 mean of every list's residuals (0 for an empty list):
+        ivf_residuals + centroid_update on a zeroed output, whole lists at a time."""
+        n, d = X.shape
+        mu = torch.zeros((self.K, d), dtype=torch.float32, device=X.device)
+        counts = torch.empty(self.K, dtype=torch.int32, device=X.device)
+        budget = max(1, _MAT_BYTES // (4 * d))
+        if n <= budget:
+            _native.centroid_update(_native.ivf_residuals(X, self.coarse, a), offsets, order, mu, counts)
+            return mu
+        off = offsets.cpu().numpy()
+        l0 = 0
+        while l0 < self.K:
+            l1 = l0 + 1
+            while l1 < self.K and off[l1 + 1] - off[l0] <= budget:
+                l1 += 1
+            rows = order[int(off[l0]):int(off[l1])].contiguous()
+            if rows.numel():
+                R = _native.ivf_residuals(_native.gather_rows(X, rows), self.coarse, a[rows.long()].contiguous())
+                _native.centroid_update(R, (offsets[l0:l1 + 1] - offsets[l0]).contiguous(),
+                                        torch.arange(rows.numel(), dtype=torch.int32, device=X.device),
+                                        mu[l0:l1], counts[l0:l1])
+            l0 = l1
+        return mu
+
+    def _fit_params(self, X: torch.Tensor, a: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor):
+        if self.kind == "sq":
+            return _native.ivf_sq_fit(X, self.coarse, offsets, order)
+        return (self._lvq_means(X, a, offsets, order),)
+
+    def _encode(self, X: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
+        if self.kind == "sq":
+            lo, den = self.params
+            return _native.ivf_sq_encode(X, self.coarse, a, lo, den, self.nbits)
+        return _native.ivf_lvq_encode(X, self.coarse, a, self.params[0], self.nbits)
+
+    def fit_lists(self, X: torch.Tensor) -> None:
+        """Assign every row, fit each list's quantizer on its residuals, encode, and lay the
+        lists out in bucket order (ids 0 .. N - 1)."""
+        n = X.shape[0]
+        a = self._assign(X)
+        offsets, order = _native.bucket_sort(a, self.K)
+        self.params = tuple(self._fit_params(X, a, offsets, order))
+        codes = self._encode(X, a)
+        row_bytes = codes.shape[1] * codes.element_size()
+        self.lists = IvfLists(
+            offsets=offsets,
+            codes=_native.gather_rows(codes, order) if row_bytes % 4 == 0 else codes[order.long()].contiguous(),
+            ids=order.clone(),
+            tau=None,
+        )
+        self.ntotal = n
+        self._index_rows()
+
+    def _index_rows(self) -> None:
+        ids = self.lists.ids.long() & 0xFFFFFFFF
+        self.pos = torch.empty(ids.numel(), dtype=torch.int64, device=ids.device)
+        self.pos[ids] = torch.arange(ids.numel(), dtype=torch.int64, device=ids.device)
+        self.list_of = torch.repeat_interleave(torch.arange(self.K, dtype=torch.int32, device=ids.device),
+                                               self.lists.offsets[1:] - self.lists.offsets[:-1]).contiguous()
+
+    def reconstruct(self, rows: torch.Tensor) -> torch.Tensor:
+        """x^ (len(rows), d) f32 of the rows with these ids, through the decode entry points."""
+        p = self.pos[rows.to(self.pos.device).long()]
+        codes = self.lists.codes[p].contiguous()
+        a = self.list_of[p].contiguous()
+        if self.kind == "sq":
+            lo, den = self.params
+            return _native.ivf_sq_decode(codes, self.coarse, a, lo, den, self.nbits)
+        return _native.ivf_lvq_decode(codes, self.coarse, a, self.params[0], self.nbits)
+
+    def probes(self, Q: torch.Tensor, nprobe: int) -> torch.Tensor:
+        nprobe = max(1, min(int(nprobe), self.K))
+        if nprobe > 256:
+            raise ValueError(f"nprobe={nprobe}: the probe selection (mivq_topk_rows) supports at most 256 lists")
+        return _native.topk_rows(_native.pairwise_distances(Q, self.coarse, self.metric), nprobe)[1]
+
+    def search(self, Q: torch.Tensor, k: int, nprobe: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(keys f32 (nq, k), ids int32 (nq, k)); L2 ascending, IP as negated inner products."""
+        L = self.lists
+        return _native.ivf_code_search(self.kind, Q, self.coarse, self.probes(Q, nprobe), L.offsets, L.codes, L.ids,
+                                       self.params, self.nbits, self.metric, k)
