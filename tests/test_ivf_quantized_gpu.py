@@ -284,6 +284,30 @@ def test_search_past_each_query_block_step(dev, oracle, kind, bits, d):
     _same(got_d, got_i, want_d, want_i, f"{kind}{bits} d={d} (QB {qb})")
 
 
+@pytest.mark.parametrize("kind,bits,metric", [("sq", 8, IR.L2), ("lvq", 4, IR.IP)])
+def test_search_in_two_chunks_of_queries(dev, oracle, kind, bits, metric):
+    """1040 queries x 256 probes x k = 256 do not fit one chunk of the workspace: the size stops
+    growing with nq, so at least the last 16 queries go through in a second chunk.  About 500 rows
+    over 256 lists (some empty), every query probing every list in its own order; skipped slots
+    leave queries of each chunk with fewer than k rows."""
+    from haag_vq import _native
+
+    d, k, nq, nlist = 8, 256, 1040, 256
+    sizes = [8] + [int(s) for s in np.random.default_rng(bits).integers(0, 5, nlist - 1)]
+    assert 0 in sizes and sum(sizes) > k
+    fn = getattr(_native.load_library(), f"mivq_ivf_{kind}_search_workspace_bytes")
+    assert 0 < fn(nq - 16, sum(sizes), nlist, nlist, d, bits, k) == fn(nq, sum(sizes), nlist, nlist, d, bits, k)
+    L = Lists(oracle, kind, bits, d, sizes=sizes, seed=21, nq=nq)
+    P = L.probes(nlist)
+    P[nq - 3, 9:] = NO_ID
+    P[nq - 2, :] = NO_ID
+    want_d, want_i = L.expected(oracle, P, metric, k)
+    assert (want_i[0] == NO_ID).all() and (want_i[nq - 2] == NO_ID).all() and (want_i[nq - 1] != NO_ID).all()
+    assert 0 < (want_i[nq - 3] != NO_ID).sum() < k
+    got_d, got_i = L.search(dev, P, metric, k)
+    _same(got_d, got_i, want_d, want_i, f"{kind}{bits} two chunks")
+
+
 # ------------------------------------------------------------------------------ the index
 def _factory(kind, bits):
     from haag_vq.methods.lvq_quantization import LVQQuantizer

@@ -216,6 +216,40 @@ def test_search_bit_exact(dev, oracle, d, qb, metric, k, nq, nprobe):
         assert np.isinf(kd[a][ki[a] == nan_id]).all()  # the NaN row's key ranks as +inf
 
 
+def test_search_in_two_chunks_of_queries(dev, oracle):
+    """1040 queries x 256 probes x k = 256 do not fit one chunk of the workspace: the size stops
+    growing with nq, so at least the last 16 queries go through in a second chunk.  512 rows of the
+    constructed set, re-dealt over 256 lists (some empty), every query probing every list in its
+    own order; skipped slots leave a query of each chunk with fewer than k rows."""
+    from haag_vq import _native
+
+    d, qb, metric, k, nq, nlist, n = 32, 4, 1, 256, 1040, 256, 512
+    fn = _native.load_library().mivq_ivf_rabitq_search_workspace_bytes
+    assert 0 < fn(nq - 16, n, nlist, nlist, d, k) == fn(nq, n, nlist, nlist, d, k)
+    C = _constructed(dev, oracle, d, metric)
+    rng = np.random.default_rng([d, nlist])
+    X = C["X"][~np.isnan(C["X"]).any(1)][:n]
+    coarse = (X[rng.choice(n, nlist, replace=False)] + 0.1 * rng.standard_normal((nlist, d))).astype(np.float32)
+    assign = rng.integers(0, nlist, n)
+    offsets, order = IR.bucket_order(oracle, assign, nlist)
+    assert (np.diff(offsets) == 0).any() and np.diff(offsets).max() > 1
+    codes = _h(_native.ivf_rabitq_encode(_t(X, dev), _t(coarse, dev), _t(assign.astype(np.int32), dev), metric))
+    D = dict(coarse=coarse, offsets=offsets, list_codes=np.ascontiguousarray(codes[order]),
+             list_ids=order.astype(np.uint32))
+    Q = (X[rng.integers(0, n, nq)] + 0.05 * rng.standard_normal((nq, d))).astype(np.float32)
+    P = np.stack([rng.permutation(nlist) for _ in range(nq)]).astype(np.int64)
+    P[5, 40:] = NO_ID
+    P[nq - 3, 9:] = NO_ID
+    P[nq - 2, :] = NO_ID
+    P = P.astype(np.uint32)
+    rd, ri = IR.expected(oracle, D["list_codes"], D["list_ids"], offsets, coarse, Q, P, qb, metric, k)
+    assert 0 < (ri[5] != NO_ID).sum() < k and 0 < (ri[nq - 3] != NO_ID).sum() < k and (ri[nq - 2] == NO_ID).all()
+    assert (ri[nq - 1] != NO_ID).all()
+    kd, ki = _search(dev, D, Q, P, qb, metric, k)
+    np.testing.assert_array_equal(ki, ri)
+    np.testing.assert_array_equal(_bits(kd), _bits(rd))
+
+
 def test_duplicate_rows_rank_by_id(dev, oracle):
     """Equal rows of one list have equal codes and keys: the smaller id comes first, next to it."""
     D = _constructed(dev, oracle, 96, 1)

@@ -1,8 +1,9 @@
 """Interleaved A/B of one entry point between two builds of libmivq.so (same process, same data).
 
-usage: python tools/ab_lib.py OTHER.so [--what encode|adc|lut|flat|sq|rabitq|lvq|pairwise]
+usage: python tools/ab_lib.py OTHER.so [--what encode|adc|lut|flat|sq|rabitq|lvq|pairwise|ivf_rabitq|ivf_sq|ivf_lvq]
                               [--n 1000000] [--d 1536] [--M 16] [--data gaussian] [--reps 10]
                               [--nq 1000] [--k 10] [--metric l2|ip] [--nbits 8] [--this THIS.so]
+                              [--nlist 1024] [--nprobe 16] [--qb 4]
 The in-tree library (vector-quantization_amd/lib/libmivq.so) is "this"; OTHER.so is e.g. a
 build of the previous commit (git stash; make; cp lib/libmivq.so /tmp/old.so; git stash pop).
 --this names another build in its place (the same file as OTHER.so: an A/A pass, the noise floor
@@ -15,6 +16,9 @@ checks that both builds give identical outputs:
             mivq_rabitq_flat_search, mivq_lvq_flat_search (SQ / LVQ: --nbits) of --nq queries
             over seeded random rows / codes, ids and distances
   pairwise  mivq_pairwise_distances of --n rows against --nq rows, the whole matrix
+  ivf_rabitq, ivf_sq, ivf_lvq   the searches over probed lists mivq_ivf_rabitq_search (--qb),
+            mivq_ivf_sq_search, mivq_ivf_lvq_search (--nbits): seeded random code rows in --nlist lists
+            of seeded uneven sizes, --nprobe random distinct lists per query, no training; ids and keys
 """
 import argparse
 import ctypes
@@ -88,6 +92,9 @@ EXACT = {
 }
 
 
+IVF = ("ivf_rabitq", "ivf_sq", "ivf_lvq")
+
+
 def exact_leg(a, libs, dev, st):
     """run(k) and outputs() of an exact search or of mivq_pairwise_distances."""
     metric = _native.METRIC_L2 if a.metric == "l2" else _native.METRIC_INNER_PRODUCT
@@ -115,6 +122,46 @@ def exact_leg(a, libs, dev, st):
         mid = [_ptr(v) if isinstance(v, torch.Tensor) else v for v in params]
         rc = getattr(libs[k], name)(_ptr(Q), a.nq, _ptr(db), a.n, a.d, *mid, metric, a.k, 0, _ptr(ws), ws.numel(),
                                     _ptr(od), _ptr(oi), P(st))
+        assert rc == 0, (rc, libs[k].mivq_last_error())
+
+    return run, lambda k: bufs[k][1:]
+
+
+def ivf_leg(a, libs, dev, st):
+    """run(k) and outputs() of a search over probed lists of constructed code rows."""
+    metric = _native.METRIC_L2 if a.metric == "l2" else _native.METRIC_INNER_PRODUCT
+    g = torch.Generator(device=dev).manual_seed(11)
+    w = torch.rand(a.nlist, device=dev, generator=g) ** 2 + 0.05  # list sizes from 1 to about 20 shares
+    sizes = (w / w.sum() * a.n).long()
+    sizes[0] += a.n - sizes.sum()
+    offsets = torch.cat([sizes.new_zeros(1), sizes.cumsum(0)])
+    ids = torch.randperm(a.n, device=dev, generator=g).to(torch.int32)
+    probe_l = torch.rand((a.nq, a.nlist), device=dev, generator=g).argsort(1)[:, :a.nprobe].to(torch.int32).contiguous()
+    Q = synth(a.nq, a.d, 7, dev, kind=a.data)
+    coarse = synth(a.nlist, a.d, 9, dev)
+    par = synth(a.nlist, a.d, 3, dev)
+    if a.what == "ivf_rabitq":
+        codes, mid, extra = _rows(a.n, (a.d + 7) // 8, 1, 5, dev), [a.qb], []
+    elif a.what == "ivf_sq":
+        codes = _rows(a.n, {4: (a.d + 1) // 2, 8: a.d, 16: 2 * a.d}[a.nbits], 0, 5, dev)
+        mid, extra = [par, par.abs() + 0.5, a.nbits], [a.nbits]
+    else:
+        codes, mid, extra = _rows(a.n, (a.d * a.nbits + 7) // 8, 1, 5, dev), [par, a.nbits], [a.nbits]
+    name = f"mivq_{a.what}_search"
+    bufs = {}
+    for k, lb in libs.items():
+        nb = getattr(lb, name + "_workspace_bytes")(a.nq, a.n, a.nlist, a.nprobe, a.d, *extra, a.k)
+        assert nb > 0, name
+        bufs[k] = (torch.empty(nb, dtype=torch.uint8, device=dev),
+                   torch.empty((a.nq, a.k), dtype=torch.float32, device=dev),
+                   torch.empty((a.nq, a.k), dtype=torch.int32, device=dev))
+
+    def run(k):
+        ws, od, oi = bufs[k]
+        args = [_ptr(v) if isinstance(v, torch.Tensor) else v for v in mid]
+        rc = getattr(libs[k], name)(_ptr(Q), a.nq, a.d, _ptr(coarse), a.nlist, _ptr(probe_l), a.nprobe, _ptr(offsets),
+                                    _ptr(codes), _ptr(ids), *args, metric, a.k, _ptr(ws), ws.numel(), _ptr(od), _ptr(oi),
+                                    P(st))
         assert rc == 0, (rc, libs[k].mivq_last_error())
 
     return run, lambda k: bufs[k][1:]
@@ -181,16 +228,20 @@ def main():
     ap.add_argument("--M", type=int, default=16)
     ap.add_argument("--data", default="gaussian")
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--what", choices=("encode", "adc", "lut", "pairwise", *EXACT), default="encode")
+    ap.add_argument("--what", choices=("encode", "adc", "lut", "pairwise", *EXACT, *IVF), default="encode")
     ap.add_argument("--nq", type=int, default=1000)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--metric", choices=("l2", "ip"), default="l2")
     ap.add_argument("--nbits", type=int, default=8)
+    ap.add_argument("--nlist", type=int, default=1024)
+    ap.add_argument("--nprobe", type=int, default=16)
+    ap.add_argument("--qb", type=int, default=4)
     a = ap.parse_args()
     dev = _native.require_device()
     libs = {k: bind(p if Path(p).is_absolute() else ROOT / p) for k, p in (("this", a.this), ("other", a.other))}
     st = torch.cuda.current_stream().cuda_stream
-    run, outputs = (pq_leg if a.what in ("encode", "adc", "lut") else exact_leg)(a, libs, dev, st)
+    leg = pq_leg if a.what in ("encode", "adc", "lut") else ivf_leg if a.what in IVF else exact_leg
+    run, outputs = leg(a, libs, dev, st)
     for k in libs:
         run(k)
     torch.cuda.synchronize()

@@ -19,6 +19,7 @@
 //   ivfpq_scan_kernel      one workgroup per (query, probe slice); 16 waves share the
 //                          query's LUT in LDS and scan whole lists, 64 codes per step, into
 //                          wave-resident top-k lists that topk_merge_kernel merges.
+#include "ivf_internal.h"
 #include "mivq_common.h"
 #include "topk.h"
 
@@ -106,19 +107,8 @@ __global__ __launch_bounds__(1024) void bucket_offsets_kernel(const int64_t* __r
     __syncthreads();
     for (int base = 0; base < K; base += 1024) {
         const int l = base + threadIdx.x;
-        const int64_t v = l < K ? tot[l] : 0;
-        part[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {  // Hillis-Steele inclusive scan
-            const int64_t add = threadIdx.x >= o ? part[threadIdx.x - o] : 0;
-            __syncthreads();
-            part[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (l < K) offsets[l] = carry + part[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += part[1023];
-        __syncthreads();
+        const int64_t first = scan1024_carry(l < K ? tot[l] : 0, part, &carry);
+        if (l < K) offsets[l] = first;
     }
     if (threadIdx.x == 0) offsets[K] = carry;
 }

@@ -12,18 +12,13 @@
 //   ivf_sq_fit_kernel     one workgroup per list: min / max of the residuals in every dimension.
 //   sq_/lvq_encode_kernel, sq_/lvq_decode_kernel <PER_ROW>: the flat kernels (code_internal.h)
 //                         with the parameters and the centroid of row i taken at assign[i].
-//   ivf_code_prep_kernel  per (query, probe slot) pair: its sort key (its list; skipped slots go
-//                         to a bucket of their own) and the sentinel fill of its partial lists.
-//   mivq_bucket_sort      stable sort of the pairs by list: the pairs probing a list are contiguous.
-//   ivf_items_kernel      per-list pair counts -> work items (list, block of QB pairs).
-//   ivf_code_scan_kernel  grid (item bound, S row ranges of the list): the QB query rows and the
-//                         list's parameter rows and centroid in LDS, lane = row, the row read
-//                         once by scan_row (code_internal.h: the loads and chains of
-//                         code_scan_kernel), WaveTopK selection inside the scan, the waves' lists
-//                         merged in LDS into one list per (pair, range).
-//   topk_merge_kernel     merges the nprobe x S partial lists of every query.
-// List sizes live on the device: the grids are sized from the shape, the kernels find their work
-// from offsets and the item table.  Queries are processed in chunks so the workspace stays bounded.
+//   ivf_code_prep_kernel  the driver's pair prologue, nothing else.
+//   ivf_code_scan_kernel  the QB query rows and the list's parameter rows and centroid in LDS,
+//                         lane = row, the row read once by scan_row (code_internal.h: the loads
+//                         and chains of code_scan_kernel), WaveTopK selection inside the scan, the
+//                         waves' lists merged in LDS into one list per (pair, range).
+// The search runs on the probed-list driver (ivf_internal.h): pair sort, work items (QB pairs
+// each), chunks of queries and the merge of the partial lists are its steps.
 #include "adc_internal.h"
 #include "code_internal.h"
 #include "ivf_internal.h"
@@ -107,46 +102,22 @@ void launch_ivf_lvq_encode(const float* x, int64_t n, int d, const float* coarse
 
 // ---------------------------------------------------------------- search
 constexpr int kIcWaves = 8;      // waves per scan workgroup: 512 rows per step
-constexpr int kIcMaxSplit = 8;   // row ranges per list at most
 constexpr int kIcTile = kIcWaves * 64;
 
-// One workgroup per pair p = a * nprobe + j of the chunk.  keys[p]: the pair's list, nlist for a
-// skipped slot (0xFFFFFFFF, or any id >= nlist).  The pair's S partial lists, part j * S + s of
-// the (parts, nqc, k) layout, are set to the sentinel: the scan writes only the (pair, range)
-// lists that hold rows.
 __global__ __launch_bounds__(64) void ivf_code_prep_kernel(const uint32_t* __restrict__ probe_l, int nlist, int nprobe,
                                                            int64_t nqc, int S, int k, uint32_t* __restrict__ keys,
                                                            float* __restrict__ pd, uint32_t* __restrict__ pi) {
-    const int64_t p = blockIdx.x;
-    const int64_t a = p / nprobe;
-    const int j = (int)(p - a * nprobe);
-    const uint32_t l = probe_l[p];
-    if (threadIdx.x == 0) keys[p] = l < (uint32_t)nlist ? l : (uint32_t)nlist;
-    for (int s = 0; s < S; ++s) {
-        const int64_t base = (((int64_t)j * S + s) * nqc + a) * k;
-        for (int e = threadIdx.x; e < k; e += 64) {
-            pd[base + e] = INFINITY;
-            pi[base + e] = kNoId;
-        }
-    }
+    int64_t a;
+    ivf_pair_prologue(probe_l, nlist, nprobe, nqc, S, k, keys, pd, pi, &a);
 }
 
 struct IcScan {
-    const float* q;          // (nqc, d) the chunk's queries
-    const float* coarse;     // (nlist, d)
-    const float* ga;         // (nlist, d) SQ den / LVQ mu
-    const float* gb;         // (nlist, d) SQ lo
-    const int64_t* poff;     // sorted-pair offsets per list
-    const uint32_t* porder;  // sorted position -> pair
-    const uint2* items;
-    const uint32_t* nitems;
-    const int64_t* offsets;  // (nlist + 1) list offsets
-    const uint8_t* codes;    // (n, row bytes) bucket order
-    const uint32_t* ids;     // (n,)
-    float* pd;               // (nprobe * S, nqc, k) partial lists
-    uint32_t* pi;
-    int64_t nqc;
-    int d, nprobe, metric, k, S, wide, narrow;
+    IvfScan s;
+    const float* q;       // (nqc, d) the chunk's queries
+    const float* coarse;  // (nlist, d)
+    const float* ga;      // (nlist, d) SQ den / LVQ mu
+    const float* gb;      // (nlist, d) SQ lo
+    int d, metric, wide, narrow;
 };
 
 // Grid (item bound, S), 512 threads.  Work item (list l, pairs [pb, pb + np)), row range s of the
@@ -160,16 +131,10 @@ __global__ __launch_bounds__(kIcWaves * 64) void ivf_code_scan_kernel(const IcSc
     using F = Fmt<FMT>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (blockIdx.x >= *A.nitems) return;
-    const uint2 item = A.items[blockIdx.x];
-    const uint32_t l = item.x;
-    const int64_t pb0 = item.y;
-    const int np = (int)min<int64_t>(QB, A.poff[l + 1] - pb0);
-    const int64_t beg = A.offsets[l], end = A.offsets[l + 1];
-    const int s = blockIdx.y;
-    const int64_t per = ((end - beg + A.S - 1) / A.S + kIcTile - 1) / kIcTile * kIcTile;
-    const int64_t rb = beg + s * per, re = min<int64_t>(end, rb + per);
-    if (np <= 0 || rb >= re) return;  // the range holds no rows: the sentinel lists stand
+    if (A.s.past_items()) return;
+    const IvfItem it = ivf_item<QB, kIcTile>(A.s);
+    if (it.empty()) return;
+    const auto [l, pb0, np, rb, re] = it;
     const int d = A.d, dp = (d + 3) & ~3;
     float* qv = smem;                        // [QB][dp]
     float* pa = smem + QB * dp;              // SQ den / LVQ mu
@@ -177,10 +142,10 @@ __global__ __launch_bounds__(kIcWaves * 64) void ivf_code_scan_kernel(const IcSc
     float* pc = pa + F::kParams * dp;        // the list's centroid
     int64_t op[QB];  // the block's pairs (uniform); slots past np repeat pair 0 (in range), never stored
 #pragma unroll
-    for (int qq = 0; qq < QB; ++qq) op[qq] = A.porder[pb0 + (qq < np ? qq : 0)];
+    for (int qq = 0; qq < QB; ++qq) op[qq] = A.s.porder[pb0 + (qq < np ? qq : 0)];
 #pragma unroll
     for (int qq = 0; qq < QB; ++qq) {
-        const float* qr = A.q + (op[qq] / A.nprobe) * d;
+        const float* qr = A.q + (op[qq] / A.s.nprobe) * d;
         for (int t = tid; t < d; t += kIcWaves * 64) qv[qq * dp + t] = qr[t];
     }
     for (int t = tid; t < d; t += kIcWaves * 64) {
@@ -199,7 +164,7 @@ __global__ __launch_bounds__(kIcWaves * 64) void ivf_code_scan_kernel(const IcSc
         thr_i[qq] = kNoId;
     }
     const bool l2 = A.metric == MIVQ_METRIC_L2;
-    const int k = A.k;
+    const int k = A.s.k;
     const int64_t stride = F::row_bytes(d);
     const ScanRows rows{qv, pa, pb, pc, dp};
     for (int64_t base = rb + (int64_t)wv * 64; base < re; base += kIcTile) {
@@ -210,8 +175,8 @@ __global__ __launch_bounds__(kIcWaves * 64) void ivf_code_scan_kernel(const IcSc
         for (int qq = 0; qq < QB; ++qq) dist[qq] = 0.0f;
         uint32_t gid = kNoId;
         if (valid) {
-            gid = A.ids[row];
-            scan_row<FMT, QB, true>(A.codes + row * stride, d, rows, A.wide, A.narrow, l2, dist);
+            gid = A.s.ids[row];
+            scan_row<FMT, QB, true>(A.s.codes + row * stride, d, rows, A.wide, A.narrow, l2, dist);
         }
 #pragma unroll
         for (int qq = 0; qq < QB; ++qq) {
@@ -238,10 +203,8 @@ __global__ __launch_bounds__(kIcWaves * 64) void ivf_code_scan_kernel(const IcSc
                 const bool valid = e < total;
                 top[qq].offer(valid, valid ? md[e] : INFINITY, valid ? mi[e] : kNoId, k, lane, thr_d[qq], thr_i[qq]);
             }
-            const int64_t a = op[qq] / A.nprobe;
-            const int64_t j = op[qq] - a * A.nprobe;
-            const int64_t obase = ((j * A.S + s) * A.nqc + a) * k;
-            top[qq].store(A.pd + obase, A.pi + obase, k, lane);
+            const int64_t obase = A.s.part_base(op[qq], blockIdx.y);
+            top[qq].store(A.s.pd + obase, A.s.pi + obase, k, lane);
         }
         __syncthreads();  // the buffer is rewritten for the next pair
     }
@@ -251,60 +214,21 @@ __global__ __launch_bounds__(kIcWaves * 64) void ivf_code_scan_kernel(const IcSc
 // the list's centroid; the budget is the one of the flat code scan (128 KiB, 160 at one query).
 ScanPolicy ic_policy(bool lvq) { return ScanPolicy{(lvq ? 1 : 2) + 1, 128, true}; }
 
-// Workspace of one search, sized on shape alone.  Queries are processed nqc at a time.
-struct IcLayout {
-    int64_t nqc;  // queries per chunk
-    int S;        // row ranges per list
-    int QB;       // pairs per work item; 0: d does not fit the LDS
-    size_t keys, porder, poff, items, nitems, sortws, pd, pi, total;
-};
-
-constexpr size_t kIcBudget = (size_t)1 << 29;  // aim of the chunking: 512 MiB
-constexpr size_t kIcCap = (size_t)1 << 30;     // never above 1 GiB
-
-IcLayout ic_layout(int64_t nq, int nlist, int nprobe, int d, int k, bool lvq) {
-    nq = std::max<int64_t>(nq, 1);
-    IcLayout L{};
-    L.QB = scan_qb(d, ic_policy(lvq));
-    if (L.QB == 0) return L;
-    // no wider than the pairs a list can expect: a workgroup computes all QB chains of a row
-    const int64_t per_list = ceil_div(nq * nprobe, nlist);
-    while (L.QB > 1 && L.QB / 2 >= per_list) L.QB /= 2;
-    const int QB = L.QB;
-    // few pairs: split the lists into row ranges so that the chip still has workgroups to run
-    const int64_t blocks = ceil_div(nq * nprobe, QB);
-    const int S = (int)std::max<int64_t>(1, std::min<int64_t>(kIcMaxSplit, ceil_div(2048, blocks)));
-    auto build = [&](int64_t nqc) {
-        IcLayout B{};
-        B.nqc = nqc;
-        B.S = S;
-        B.QB = QB;
-        const size_t P = (size_t)nqc * nprobe;
-        size_t off = 0;
-        B.keys = off;   off = align_up(off + P * 4, 256);
-        B.porder = off; off = align_up(off + P * 4, 256);
-        B.poff = off;   off = align_up(off + ((size_t)nlist + 2) * 8, 256);
-        B.items = off;  off = align_up(off + ((size_t)ceil_div(P, QB) + nlist) * 8, 256);
-        B.nitems = off; off += 256;
-        B.sortws = off; off = align_up(off + mivq_bucket_sort_workspace_bytes((int64_t)P, nlist + 1), 256);
-        B.pd = off;     off = align_up(off + P * S * k * 4, 256);
-        B.pi = off;     off = align_up(off + P * S * k * 4, 256);
-        B.total = off;
-        return B;
-    };
-    const size_t per_query = (size_t)nprobe * (16 + (size_t)S * k * 8);
-    int64_t nqc = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(kIcBudget / per_query)));
-    L = build(nqc);
-    while (L.total > kIcCap && nqc > 1) {
-        nqc = (nqc + 1) / 2;
-        L = build(nqc);
-    }
-    return L;
+// Pairs per work item: the scan's query block, no wider than the pairs a list can expect (a
+// workgroup computes all QB chains of a row); 0: d does not fit the LDS.
+int ic_pairs_per_item(int64_t nq, int nlist, int nprobe, int d, bool lvq) {
+    int QB = scan_qb(d, ic_policy(lvq));
+    const int64_t per_list = ceil_div(std::max<int64_t>(nq, 1) * nprobe, nlist);
+    while (QB > 1 && QB / 2 >= per_list) QB /= 2;
+    return QB;
 }
 
-bool ic_sizes_ok(int64_t nq, int64_t n, int32_t nlist, int32_t nprobe, int32_t d) {
-    return nq >= 0 && n >= 0 && nlist > 0 && nprobe > 0 && d > 0 && d <= (1 << 27);
+// 0: d does not fit the LDS.
+size_t ic_workspace_bytes(int64_t nq, int nlist, int nprobe, int d, int k, bool lvq) {
+    const int QB = ic_pairs_per_item(nq, nlist, nprobe, d, lvq);
+    return QB == 0 ? 0 : ivf_layout(nq, nlist, nprobe, k, QB, 0, 0, 16).total;
 }
+
 bool sq_bits_ok(int nbits) { return nbits == 4 || nbits == 8 || nbits == 16; }
 bool lvq_bits_ok(int nbits) { return nbits >= 1 && nbits <= 8; }
 
@@ -312,17 +236,11 @@ template <int FMT, int R, int QB>
 hipError_t launch_ic_scan(const IcScan& A, int64_t maxitems, hipStream_t st) {
     using F = Fmt<FMT>;
     const size_t rows = (size_t)(QB + F::kParams + 1) * ((A.d + 3) & ~3) * sizeof(float);
-    const size_t smem = std::max(rows, (size_t)(kIcWaves - 1) * A.k * 8);
+    const size_t smem = std::max(rows, (size_t)(kIcWaves - 1) * A.s.k * 8);
     auto kern = ivf_code_scan_kernel<FMT, R, QB>;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)maxitems, (unsigned)A.S), dim3(kIcWaves * 64), smem, st, A);
-    return hipGetLastError();
-}
-
-template <int QB>
-hipError_t launch_ic_items(const int64_t* poff, int nlist, uint2* items, uint32_t* nitems, hipStream_t st) {
-    hipLaunchKernelGGL(ivf_items_kernel<QB>, dim3(1), dim3(1024), 0, st, poff, nlist, items, nitems);
+    hipLaunchKernelGGL(kern, dim3((unsigned)maxitems, (unsigned)A.s.S), dim3(kIcWaves * 64), smem, st, A);
     return hipGetLastError();
 }
 
@@ -333,64 +251,38 @@ int ivf_code_search(const char* name, const float* q, int64_t nq, int d, const f
                     const uint32_t* list_ids, const float* ga, const float* gb, int metric, int k, void* workspace,
                     size_t workspace_bytes, float* dists, uint32_t* ids, void* stream) {
     using F = Fmt<FMT>;
-    const IcLayout L = ic_layout(nq, nlist, nprobe, d, k, F::kIsLvq);
-    MIVQ_REQUIRE(workspace_bytes >= L.total, MIVQ_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", name, workspace_bytes,
-                 L.total);
     hipStream_t st = as_stream(stream);
-    unsigned char* p = static_cast<unsigned char*>(workspace);
-    uint32_t* keys = reinterpret_cast<uint32_t*>(p + L.keys);
-    uint32_t* porder = reinterpret_cast<uint32_t*>(p + L.porder);
-    int64_t* poff = reinterpret_cast<int64_t*>(p + L.poff);
-    uint2* items = reinterpret_cast<uint2*>(p + L.items);
-    uint32_t* nitems = reinterpret_cast<uint32_t*>(p + L.nitems);
-    float* pd = reinterpret_cast<float*>(p + L.pd);
-    uint32_t* pi = reinterpret_cast<uint32_t*>(p + L.pi);
     const uintptr_t addr = reinterpret_cast<uintptr_t>(list_codes);
     const int rbytes = F::row_bytes(d);
     const int wb = F::kWideWords * 4;
     const int wide = addr % wb == 0 && rbytes % wb == 0;
     const int narrow = addr % 4 == 0 && rbytes % 4 == 0;
-    for (int64_t a0 = 0; a0 < nq; a0 += L.nqc) {
-        const int64_t nqc = std::min<int64_t>(L.nqc, nq - a0);
-        const int64_t P = nqc * nprobe;
-        hipLaunchKernelGGL(ivf_code_prep_kernel, dim3((unsigned)P), dim3(64), 0, st, probe_l + a0 * nprobe, nlist, nprobe,
-                           nqc, L.S, k, keys, pd, pi);
-        int rc = check_launch(name);
-        if (rc) return rc;
-        rc = mivq_bucket_sort(keys, P, nlist + 1, poff, porder, p + L.sortws, L.pd - L.sortws, stream);
-        if (rc) return rc;
-        hipError_t e = with_query_block(L.QB, [&](auto QB) {
-            return launch_ic_items<decltype(QB)::value>(poff, nlist, items, nitems, st);
-        });
-        if (e != hipSuccess) return set_error(MIVQ_ERR_HIP, "%s (items): %s", name, hipGetErrorString(e));
-        const IcScan A{q + a0 * d, coarse, ga, gb, poff, porder, items, nitems, offsets, list_codes, list_ids,
-                       pd, pi, nqc, d, nprobe, metric, k, L.S, wide, narrow};
-        e = with_topk_regs(k, [&](auto R) {
-            return with_query_block(L.QB, [&](auto QB) {
-                return launch_ic_scan<FMT, decltype(R)::value, decltype(QB)::value>(A, ceil_div(P, L.QB) + nlist, st);
+    return with_query_block(ic_pairs_per_item(nq, nlist, nprobe, d, F::kIsLvq), [&](auto QB) {
+        constexpr int kQB = decltype(QB)::value;
+        const IvfLayout L = ivf_layout(nq, nlist, nprobe, k, kQB, 0, 0, 16);
+        return ivf_probed_search<kQB>(
+            name, L, nq, nlist, nprobe, k, offsets, list_codes, list_ids, workspace, workspace_bytes, dists, ids, stream,
+            [&](const IvfChunk& c) {
+                hipLaunchKernelGGL(ivf_code_prep_kernel, dim3((unsigned)c.pairs), dim3(64), 0, st,
+                                   probe_l + c.a0 * nprobe, nlist, nprobe, c.nqc, L.S, k, c.keys, c.scan.pd, c.scan.pi);
+                return hipGetLastError();
+            },
+            [&](const IvfChunk& c, int64_t maxitems) {
+                const IcScan A{c.scan, q + c.a0 * d, coarse, ga, gb, d, metric, wide, narrow};
+                return with_topk_regs(
+                    k, [&](auto R) { return launch_ic_scan<FMT, decltype(R)::value, kQB>(A, maxitems, st); });
             });
-        });
-        if (e != hipSuccess) return set_error(MIVQ_ERR_HIP, "%s (scan): %s", name, hipGetErrorString(e));
-        e = launch_topk_merge(pd, pi, nprobe * L.S, nqc, k, dists + a0 * k, ids + a0 * k, st);
-        if (e != hipSuccess) return set_error(MIVQ_ERR_HIP, "%s (merge): %s", name, hipGetErrorString(e));
-    }
-    return MIVQ_OK;
+    });
 }
 
-// The checks both searches share, before any launch; *done: nothing to do (nq == 0).
+// The checks both searches share, before any launch.
 int ic_search_prologue(const char* name, int64_t nq, int d, int nlist, int nprobe, bool bits_ok, int nbits, bool lvq,
-                       int metric, int k, bool* done) {
-    *done = false;
-    MIVQ_REQUIRE(ic_sizes_ok(nq, 0, nlist, nprobe, d), MIVQ_ERR_INVALID, "%s: bad sizes nq=%lld d=%d nlist=%d nprobe=%d",
-                 name, (long long)nq, d, nlist, nprobe);
+                       int metric, int k) {
+    const int rc = ivf_search_check(name, nq, d, 1 << 27, nlist, nprobe, k, metric);
+    if (rc != MIVQ_OK) return rc;
     MIVQ_REQUIRE(bits_ok, MIVQ_ERR_INVALID, lvq ? "num_bits must be in [1, 8], got %d" : "num_bits must be 4, 8, or 16, got %d",
                  nbits);
-    MIVQ_REQUIRE(k >= 1 && k <= 256, MIVQ_ERR_UNSUPPORTED, "%s: k=%d not in [1, 256]", name, k);
-    MIVQ_REQUIRE(metric == MIVQ_METRIC_L2 || metric == MIVQ_METRIC_INNER_PRODUCT, MIVQ_ERR_UNSUPPORTED, "%s: metric %d",
-                 name, metric);
-    MIVQ_REQUIRE(nlist <= 16383, MIVQ_ERR_UNSUPPORTED, "%s: nlist=%d > 16383", name, nlist);
     MIVQ_REQUIRE(scan_qb(d, ic_policy(lvq)) > 0, MIVQ_ERR_UNSUPPORTED, "%s: d=%d too large for LDS", name, d);
-    *done = nq == 0;
     return MIVQ_OK;
 }
 
@@ -484,14 +376,14 @@ extern "C" int mivq_ivf_lvq_decode(const uint8_t* codes, int64_t n, int32_t d, c
 
 extern "C" size_t mivq_ivf_sq_search_workspace_bytes(int64_t nq, int64_t n, int32_t nlist, int32_t nprobe, int32_t d,
                                                      int32_t nbits, int32_t k) {
-    if (!ic_sizes_ok(nq, n, nlist, nprobe, d) || !sq_bits_ok(nbits) || k <= 0 || k > 256 || nlist > 16383) return 0;
-    return ic_layout(nq, nlist, nprobe, d, k, false).total;
+    if (!ivf_shape_ok(nq, n, nlist, nprobe, d, k) || d > (1 << 27) || !sq_bits_ok(nbits)) return 0;
+    return ic_workspace_bytes(nq, nlist, nprobe, d, k, false);
 }
 
 extern "C" size_t mivq_ivf_lvq_search_workspace_bytes(int64_t nq, int64_t n, int32_t nlist, int32_t nprobe, int32_t d,
                                                       int32_t nbits, int32_t k) {
-    if (!ic_sizes_ok(nq, n, nlist, nprobe, d) || !lvq_bits_ok(nbits) || k <= 0 || k > 256 || nlist > 16383) return 0;
-    return ic_layout(nq, nlist, nprobe, d, k, true).total;
+    if (!ivf_shape_ok(nq, n, nlist, nprobe, d, k) || d > (1 << 27) || !lvq_bits_ok(nbits)) return 0;
+    return ic_workspace_bytes(nq, nlist, nprobe, d, k, true);
 }
 
 extern "C" int mivq_ivf_sq_search(const float* q, int64_t nq, int32_t d, const float* coarse, int32_t nlist,
@@ -499,9 +391,8 @@ extern "C" int mivq_ivf_sq_search(const float* q, int64_t nq, int32_t d, const f
                                   const uint32_t* list_ids, const float* lo, const float* den, int32_t nbits,
                                   int32_t metric, int32_t k, void* workspace, size_t workspace_bytes, float* dists,
                                   uint32_t* ids, void* stream) {
-    bool done = false;
-    const int rc = ic_search_prologue("ivf_sq_search", nq, d, nlist, nprobe, sq_bits_ok(nbits), nbits, false, metric, k, &done);
-    if (rc != MIVQ_OK || done) return rc;
+    const int rc = ic_search_prologue("ivf_sq_search", nq, d, nlist, nprobe, sq_bits_ok(nbits), nbits, false, metric, k);
+    if (rc != MIVQ_OK || nq == 0) return rc;
     MIVQ_REQUIRE(q && coarse && probe_l && offsets && list_codes && list_ids && lo && den && dists && ids && workspace,
                  MIVQ_ERR_INVALID, "ivf_sq_search: null pointer");
     MIVQ_REQUIRE(nbits != 16 || reinterpret_cast<uintptr_t>(list_codes) % 2 == 0, MIVQ_ERR_INVALID,
@@ -521,9 +412,8 @@ extern "C" int mivq_ivf_lvq_search(const float* q, int64_t nq, int32_t d, const 
                                    const uint8_t* list_codes, const uint32_t* list_ids, const float* mu, int32_t nbits,
                                    int32_t metric, int32_t k, void* workspace, size_t workspace_bytes, float* dists,
                                    uint32_t* ids, void* stream) {
-    bool done = false;
-    const int rc = ic_search_prologue("ivf_lvq_search", nq, d, nlist, nprobe, lvq_bits_ok(nbits), nbits, true, metric, k, &done);
-    if (rc != MIVQ_OK || done) return rc;
+    const int rc = ic_search_prologue("ivf_lvq_search", nq, d, nlist, nprobe, lvq_bits_ok(nbits), nbits, true, metric, k);
+    if (rc != MIVQ_OK || nq == 0) return rc;
     MIVQ_REQUIRE(q && coarse && probe_l && offsets && list_codes && list_ids && mu && dists && ids && workspace,
                  MIVQ_ERR_INVALID, "ivf_lvq_search: null pointer");
 #define MIVQ_IVF_LVQ_SEARCH(B)                                                                                        \

@@ -848,7 +848,6 @@ def ivfpq_search(lut: torch.Tensor, probe_d: torch.Tensor, probe_l: torch.Tensor
     return dists, ids
 
 
-
 def ivf_rabitq_encode(x: torch.Tensor, coarse: torch.Tensor, assign: torch.Tensor, metric: int,
                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """RaBitQ-1 code rows whose centre is the row's list centroid coarse[assign[i]]; bit-identical
@@ -870,6 +869,29 @@ def ivf_rabitq_encode(x: torch.Tensor, coarse: torch.Tensor, assign: torch.Tenso
     return out
 
 
+def _ivf_list_search(entry: str, what: str, q: torch.Tensor, coarse: torch.Tensor, probe_l: torch.Tensor,
+                     offsets: torch.Tensor, list_codes: torch.Tensor, list_ids: torch.Tensor, size_extra: tuple,
+                     mid: tuple, metric: int, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The call of a search over probed lists: mivq_ivf_<entry>_search with the workspace its
+    _workspace_bytes asks for.  size_extra: that query's arguments between d and k; mid: the
+    search's between list_ids and the metric.  q, coarse and list_codes are checked by the caller."""
+    _check(probe_l, "probe_l", torch.int32, 2)
+    _check(offsets, "offsets", torch.int64, 1)
+    _check(list_ids, "list_ids", torch.int32, 1)
+    nq, d = q.shape
+    nlist, nprobe = coarse.shape[0], probe_l.shape[1]
+    n = list_codes.shape[0]
+    if probe_l.shape[0] != nq or offsets.shape[0] != nlist + 1 or list_ids.shape[0] != n:
+        raise ValueError(f"{what}: shape mismatch")
+    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+    size_fn = getattr(load_library(), f"mivq_ivf_{entry}_search_workspace_bytes")
+    ws = workspace(size_fn(nq, n, nlist, nprobe, d, *size_extra, k), q.device)
+    _call(f"mivq_ivf_{entry}_search", _ptr(q), nq, d, _ptr(coarse), nlist, _ptr(probe_l), nprobe, _ptr(offsets),
+          _ptr(list_codes), _ptr(list_ids), *mid, metric, k, _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids), _stream())
+    return dists, ids
+
+
 def ivf_rabitq_search(q: torch.Tensor, coarse: torch.Tensor, probe_l: torch.Tensor, offsets: torch.Tensor,
                       list_codes: torch.Tensor, list_ids: torch.Tensor, qb: int, metric: int,
                       k: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -877,24 +899,13 @@ def ivf_rabitq_search(q: torch.Tensor, coarse: torch.Tensor, probe_l: torch.Tens
     uint32 ids), ascending; IP keys are negated estimates; missing slots hold (+inf, 0xFFFFFFFF)."""
     _check(q, "q", torch.float32, 2)
     _check(coarse, "coarse", torch.float32, 2)
-    _check(probe_l, "probe_l", torch.int32, 2)
-    _check(offsets, "offsets", torch.int64, 1)
     _check(list_codes, "list_codes", torch.uint8, 2)
-    _check(list_ids, "list_ids", torch.int32, 1)
-    nq, d = q.shape
-    nlist, nprobe = coarse.shape[0], probe_l.shape[1]
-    n = list_codes.shape[0]
+    d = q.shape[1]
     if coarse.shape[1] != d or list_codes.shape[1] != rabitq_code_size(d):
         raise ValueError(f"ivf_rabitq_search: code rows {list_codes.shape[1]} B / coarse d={coarse.shape[1]} do not "
                          f"match d={d}")
-    if probe_l.shape[0] != nq or offsets.shape[0] != nlist + 1 or list_ids.shape[0] != n:
-        raise ValueError("ivf_rabitq_search: shape mismatch")
-    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
-    ws = workspace(load_library().mivq_ivf_rabitq_search_workspace_bytes(nq, n, nlist, nprobe, d, k), q.device)
-    _call("mivq_ivf_rabitq_search", _ptr(q), nq, d, _ptr(coarse), nlist, _ptr(probe_l), nprobe, _ptr(offsets),
-          _ptr(list_codes), _ptr(list_ids), qb, metric, k, _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids), _stream())
-    return dists, ids
+    return _ivf_list_search("rabitq", "ivf_rabitq_search", q, coarse, probe_l, offsets, list_codes, list_ids, (), (qb,),
+                            metric, k)
 
 
 # ----------------------------------------------------------------- IVF over per-list SQ / LVQ codes
@@ -1011,10 +1022,7 @@ def ivf_code_search(kind: str, q: torch.Tensor, coarse: torch.Tensor, probe_l: t
     if kind not in ("sq", "lvq"):
         raise ValueError(f"ivf_code_search: kind must be 'sq' or 'lvq', got {kind!r}")
     _check(q, "q", torch.float32, 2)
-    _check(probe_l, "probe_l", torch.int32, 2)
-    _check(offsets, "offsets", torch.int64, 1)
-    _check(list_ids, "list_ids", torch.int32, 1)
-    nq, d = q.shape
+    d = q.shape[1]
     if kind == "sq":
         _sq_code_check(list_codes, d, nbits, "ivf_code_search")
         names = ("lo", "den")
@@ -1023,17 +1031,6 @@ def ivf_code_search(kind: str, q: torch.Tensor, coarse: torch.Tensor, probe_l: t
         names = ("mu",)
     if len(params) != len(names):
         raise ValueError(f"ivf_code_search: {kind} takes the parameters {names}")
-    n = list_codes.shape[0]
-    nlist, nprobe = coarse.shape[0], probe_l.shape[1]
-    _ivf_code_check(coarse, None, tuple(zip(names, params)), n, d, "ivf_code_search")
-    if probe_l.shape[0] != nq or offsets.shape[0] != nlist + 1 or list_ids.shape[0] != n:
-        raise ValueError("ivf_code_search: shape mismatch")
-    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
-    lib = load_library()
-    size_fn = lib.mivq_ivf_sq_search_workspace_bytes if kind == "sq" else lib.mivq_ivf_lvq_search_workspace_bytes
-    ws = workspace(size_fn(nq, n, nlist, nprobe, d, nbits, k), q.device)
-    _call(f"mivq_ivf_{kind}_search", _ptr(q), nq, d, _ptr(coarse), nlist, _ptr(probe_l), nprobe, _ptr(offsets),
-          _ptr(list_codes), _ptr(list_ids), *[_ptr(t) for t in params], nbits, metric, k, _ptr(ws), ws.numel(),
-          _ptr(dists), _ptr(ids), _stream())
-    return dists, ids
+    _ivf_code_check(coarse, None, tuple(zip(names, params)), list_codes.shape[0], d, "ivf_code_search")
+    return _ivf_list_search(kind, "ivf_code_search", q, coarse, probe_l, offsets, list_codes, list_ids, (nbits,),
+                            (*[_ptr(t) for t in params], nbits), metric, k)

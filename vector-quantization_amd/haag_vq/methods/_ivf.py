@@ -127,88 +127,11 @@ class IvfLists:
     tau: Optional[torch.Tensor]  # (N,) f32, L2 only
 
 
-class IvfPq:
-    """IVF with residual PQ (device-resident); the engine behind FaissIvfPqIndex."""
+class _IvfEngine:
+    """What the engines share: the coarse quantizer, the assignment of rows, the probe selection
+    and the lists in bucket order."""
 
-    def __init__(self, d: int, K: int, M: int, nbits: int = 8, metric: int = _native.METRIC_L2) -> None:
-        if d % M != 0:
-            raise AssertionError("D must be divisible by M (number of subquantizers)")
-        self.d, self.K, self.M, self.nbits, self.metric = d, K, M, nbits, metric
-        self.coarse: Optional[torch.Tensor] = None
-        self.pq: Optional[torch.Tensor] = None    # (M, ksub, dsub)
-        self.prep: Optional[torch.Tensor] = None
-        self.lists: Optional[IvfLists] = None
-        self.ntotal = 0
-
-    # --------------------------------------------------------------- train / add
-    def train(self, X: torch.Tensor, coarse_iters: int = 10, pq_iters: int = 25, seed: int = 1234) -> None:
-        self.coarse = train_coarse(X, self.K, niter=coarse_iters, seed=seed, metric=self.metric)
-        ksub = 1 << self.nbits
-        rng = np.random.default_rng(seed + 1)
-        n = X.shape[0]
-        cap = 256 * ksub
-        Xs = X if n <= cap else X[torch.from_numpy(np.sort(rng.permutation(n)[:cap])).to(X.device)].contiguous()
-        _, a = assign(Xs, self.coarse, self.metric)
-        R = _native.ivf_residuals(Xs, self.coarse, a)
-        self.pq = train_pq(R, self.M, self.nbits, niter=pq_iters, seed=seed)
-        self.prep = _native.pq_prepare(self.pq, self.nbits)
-
-    def _encode(self, X: torch.Tensor):
-        n = X.shape[0]
-        a = torch.empty(n, dtype=torch.int32, device=X.device)
-        codes = torch.empty((n, self.M), dtype=torch.uint8, device=X.device)
-        tau = torch.empty(n, dtype=torch.float32, device=X.device) if self.metric == _native.METRIC_L2 else None
-        step = max(1, min(_rows_per_chunk(self.K), (1 << 30) // (4 * self.d)))
-        for s in range(0, n, step):
-            e = min(n, s + step)
-            _, a[s:e] = assign(X[s:e], self.coarse, self.metric)
-            R = _native.ivf_residuals(X[s:e], self.coarse, a[s:e])
-            c = _native.pq_encode(R, self.pq, self.prep, self.nbits)
-            u8 = c if self.nbits == 8 else _native.pq_unpack(c, self.M, self.nbits)
-            codes[s:e] = u8
-            if tau is not None:
-                tau[s:e] = _native.ivfpq_terms(u8, self.pq, self.prep, self.coarse, a[s:e], self.nbits)
-        return a, codes, tau
-
-    def add(self, X: torch.Tensor) -> None:
-        """Append rows (ids continue from ntotal); lists are rebuilt in bucket order."""
-        a, codes, tau = self._encode(X)
-        ids = torch.arange(self.ntotal, self.ntotal + X.shape[0], dtype=torch.int64, device=X.device).to(torch.int32)
-        if self.lists is not None and self.ntotal > 0:
-            old = self.lists
-            # recover the row-order arrays of the existing lists from their bucket order
-            a_old = torch.repeat_interleave(torch.arange(self.K, dtype=torch.int32, device=X.device),
-                                            (old.offsets[1:] - old.offsets[:-1]))
-            a = torch.cat([a_old, a])
-            codes = torch.cat([old.codes, codes])
-            ids = torch.cat([old.ids, ids])
-            if tau is not None:
-                tau = torch.cat([old.tau, tau])
-        offsets, order = _native.bucket_sort(a.contiguous(), self.K)
-        self.lists = IvfLists(
-            offsets=offsets,
-            codes=_native.gather_rows(codes.contiguous(), order) if self.M % 4 == 0 else codes[order.long()].contiguous(),
-            ids=_native.gather_rows(ids.contiguous(), order),
-            tau=None if tau is None else _native.gather_rows(tau.contiguous(), order),
-        )
-        self.ntotal += X.shape[0]
-
-    # --------------------------------------------------------------- search
-    def search(self, Q: torch.Tensor, k: int, nprobe: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(dists f32 (nq, k), ids int32 (nq, k)); L2 ascending, IP as negated scores."""
-        nprobe = max(1, min(int(nprobe), self.K))
-        if nprobe > 256:
-            raise ValueError(f"nprobe={nprobe}: the probe selection (mivq_topk_rows) supports at most 256 lists")
-        pd, pl = _native.topk_rows(_native.pairwise_distances(Q, self.coarse, self.metric), nprobe)
-        lut = _native.adc_lut(Q, self.pq, self.nbits, _native.METRIC_INNER_PRODUCT)
-        L = self.lists
-        return _native.ivfpq_search(lut, pd, pl, L.offsets, L.codes, L.ids, L.tau, self.metric, k, self.nbits)
-
-
-class IvfRaBitQ:
-    """IVF over RaBitQ-1 codes (device-resident); the engine behind RaBitQIVFIndex."""
-
-    def __init__(self, d: int, K: int, metric: int = _native.METRIC_L2) -> None:
+    def __init__(self, d: int, K: int, metric: int) -> None:
         self.d, self.K, self.metric = d, K, metric
         self.coarse: Optional[torch.Tensor] = None
         self.lists: Optional[IvfLists] = None
@@ -217,50 +140,115 @@ class IvfRaBitQ:
     def train(self, X: torch.Tensor, coarse_iters: int = 10, seed: int = 1234) -> None:
         self.coarse = train_coarse(X, self.K, niter=coarse_iters, seed=seed, metric=self.metric)
 
-    def _encode(self, X: torch.Tensor):
-        n = X.shape[0]
-        a = torch.empty(n, dtype=torch.int32, device=X.device)
-        codes = torch.empty((n, _native.rabitq_code_size(self.d)), dtype=torch.uint8, device=X.device)
-        step = _rows_per_chunk(self.K)
-        for s in range(0, n, step):
-            e = min(n, s + step)
-            _, a[s:e] = assign(X[s:e], self.coarse, self.metric)
-            _native.ivf_rabitq_encode(X[s:e], self.coarse, a[s:e], self.metric, out=codes[s:e])
-        return a, codes
+    def _assign(self, X: torch.Tensor) -> torch.Tensor:
+        """The list of every row, int32 (n,)."""
+        return assign(X, self.coarse, self.metric)[1]
 
-    def add(self, X: torch.Tensor) -> None:
-        """Append rows (ids continue from ntotal); lists are rebuilt in bucket order."""
-        a, codes = self._encode(X)
-        ids = torch.arange(self.ntotal, self.ntotal + X.shape[0], dtype=torch.int64, device=X.device).to(torch.int32)
-        if self.lists is not None and self.ntotal > 0:
-            old = self.lists
-            # recover the row-order arrays of the existing lists from their bucket order
-            a_old = torch.repeat_interleave(torch.arange(self.K, dtype=torch.int32, device=X.device),
-                                            (old.offsets[1:] - old.offsets[:-1]))
-            a = torch.cat([a_old, a])
-            codes = torch.cat([old.codes, codes])
-            ids = torch.cat([old.ids, ids])
-        offsets, order = _native.bucket_sort(a.contiguous(), self.K)
-        self.lists = IvfLists(
-            offsets=offsets,
-            codes=(_native.gather_rows(codes.contiguous(), order) if codes.shape[1] % 4 == 0
-                   else codes[order.long()].contiguous()),
-            ids=_native.gather_rows(ids.contiguous(), order),
-            tau=None,
-        )
-        self.ntotal += X.shape[0]
-
-    def search(self, Q: torch.Tensor, k: int, nprobe: int, qb: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(keys f32 (nq, k), ids int32 (nq, k)); L2 estimates ascending, IP as negated estimates."""
+    def _probe(self, Q: torch.Tensor, nprobe: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The nprobe nearest lists of every query: (coarse dists f32, lists int32), both (nq, nprobe)."""
         nprobe = max(1, min(int(nprobe), self.K))
         if nprobe > 256:
             raise ValueError(f"nprobe={nprobe}: the probe selection (mivq_topk_rows) supports at most 256 lists")
-        _, pl = _native.topk_rows(_native.pairwise_distances(Q, self.coarse, self.metric), nprobe)
+        return _native.topk_rows(_native.pairwise_distances(Q, self.coarse, self.metric), nprobe)
+
+    def probes(self, Q: torch.Tensor, nprobe: int) -> torch.Tensor:
+        """The lists of _probe alone, int32 (nq, nprobe)."""
+        return self._probe(Q, nprobe)[1]
+
+    def _list_of(self) -> torch.Tensor:
+        """The list of every stored row in bucket order, from the offsets."""
+        off = self.lists.offsets
+        return torch.repeat_interleave(torch.arange(self.K, dtype=torch.int32, device=off.device), off[1:] - off[:-1])
+
+    @staticmethod
+    def _gather(rows: torch.Tensor, order: torch.Tensor) -> torch.Tensor:
+        """rows[order]; mivq_gather_rows moves rows of whole 4-byte words."""
+        rows = rows.contiguous()
+        if rows[:1].numel() * rows.element_size() % 4 == 0:
+            return _native.gather_rows(rows, order)
+        return rows[order.long()].contiguous()
+
+    def _append(self, a: torch.Tensor, codes: torch.Tensor, tau: Optional[torch.Tensor] = None) -> None:
+        """Append rows with lists a (ids continue from ntotal); the lists are rebuilt in bucket order."""
+        n = a.shape[0]
+        ids = torch.arange(self.ntotal, self.ntotal + n, dtype=torch.int64, device=a.device).to(torch.int32)
+        if self.lists is not None and self.ntotal > 0:
+            old = self.lists
+            a = torch.cat([self._list_of(), a])
+            codes = torch.cat([old.codes, codes])
+            ids = torch.cat([old.ids, ids])
+            if tau is not None:
+                tau = torch.cat([old.tau, tau])
+        offsets, order = _native.bucket_sort(a.contiguous(), self.K)
+        self.lists = IvfLists(offsets=offsets, codes=self._gather(codes, order), ids=self._gather(ids, order),
+                              tau=None if tau is None else self._gather(tau, order))
+        self.ntotal += n
+
+
+class IvfPq(_IvfEngine):
+    """IVF with residual PQ (device-resident); the engine behind FaissIvfPqIndex."""
+
+    def __init__(self, d: int, K: int, M: int, nbits: int = 8, metric: int = _native.METRIC_L2) -> None:
+        if d % M != 0:
+            raise AssertionError("D must be divisible by M (number of subquantizers)")
+        super().__init__(d, K, metric)
+        self.M, self.nbits = M, nbits
+        self.pq: Optional[torch.Tensor] = None    # (M, ksub, dsub)
+        self.prep: Optional[torch.Tensor] = None
+
+    def train(self, X: torch.Tensor, coarse_iters: int = 10, pq_iters: int = 25, seed: int = 1234) -> None:
+        super().train(X, coarse_iters, seed)
+        ksub = 1 << self.nbits
+        rng = np.random.default_rng(seed + 1)
+        n = X.shape[0]
+        cap = 256 * ksub
+        Xs = X if n <= cap else X[torch.from_numpy(np.sort(rng.permutation(n)[:cap])).to(X.device)].contiguous()
+        R = _native.ivf_residuals(Xs, self.coarse, self._assign(Xs))
+        self.pq = train_pq(R, self.M, self.nbits, niter=pq_iters, seed=seed)
+        self.prep = _native.pq_prepare(self.pq, self.nbits)
+
+    def add(self, X: torch.Tensor) -> None:
+        """Append rows (ids continue from ntotal); lists are rebuilt in bucket order."""
+        n = X.shape[0]
+        a = self._assign(X)
+        codes = torch.empty((n, self.M), dtype=torch.uint8, device=X.device)
+        tau = torch.empty(n, dtype=torch.float32, device=X.device) if self.metric == _native.METRIC_L2 else None
+        step = max(1, (1 << 30) // (4 * self.d))  # the residual buffer
+        for s in range(0, n, step):
+            e = min(n, s + step)
+            c = _native.pq_encode(_native.ivf_residuals(X[s:e], self.coarse, a[s:e]), self.pq, self.prep, self.nbits)
+            codes[s:e] = c if self.nbits == 8 else _native.pq_unpack(c, self.M, self.nbits)
+            if tau is not None:
+                tau[s:e] = _native.ivfpq_terms(codes[s:e], self.pq, self.prep, self.coarse, a[s:e], self.nbits)
+        self._append(a, codes, tau)
+
+    def search(self, Q: torch.Tensor, k: int, nprobe: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(dists f32 (nq, k), ids int32 (nq, k)); L2 ascending, IP as negated scores."""
+        pd, pl = self._probe(Q, nprobe)
+        lut = _native.adc_lut(Q, self.pq, self.nbits, _native.METRIC_INNER_PRODUCT)
         L = self.lists
-        return _native.ivf_rabitq_search(Q, self.coarse, pl, L.offsets, L.codes, L.ids, qb, self.metric, k)
+        return _native.ivfpq_search(lut, pd, pl, L.offsets, L.codes, L.ids, L.tau, self.metric, k, self.nbits)
 
 
-class IvfCodes:
+class IvfRaBitQ(_IvfEngine):
+    """IVF over RaBitQ-1 codes (device-resident); the engine behind RaBitQIVFIndex."""
+
+    def __init__(self, d: int, K: int, metric: int = _native.METRIC_L2) -> None:
+        super().__init__(d, K, metric)
+
+    def add(self, X: torch.Tensor) -> None:
+        """Append rows (ids continue from ntotal); lists are rebuilt in bucket order."""
+        a = self._assign(X)
+        self._append(a, _native.ivf_rabitq_encode(X, self.coarse, a, self.metric))
+
+    def search(self, Q: torch.Tensor, k: int, nprobe: int, qb: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(keys f32 (nq, k), ids int32 (nq, k)); L2 estimates ascending, IP as negated estimates."""
+        L = self.lists
+        return _native.ivf_rabitq_search(Q, self.coarse, self.probes(Q, nprobe), L.offsets, L.codes, L.ids, qb,
+                                         self.metric, k)
+
+
+class IvfCodes(_IvfEngine):
     """IVF over per-list SQ ('sq': 4 / 8 / 16 bits) or LVQ ('lvq': 1..8 bits) codes of the residuals
     (device-resident); the engine behind IvfQuantizedIndex.  ``params`` are (nlist, d) f32 tensors:
     (lo, den) for SQ, (mu,) for LVQ; ``pos[id]`` is the bucket position of row ``id``."""
@@ -268,24 +256,10 @@ class IvfCodes:
     def __init__(self, d: int, K: int, kind: str, nbits: int, metric: int = _native.METRIC_L2) -> None:
         if kind not in ("sq", "lvq"):
             raise ValueError(f"kind must be 'sq' or 'lvq', got {kind!r}")
-        self.d, self.K, self.kind, self.nbits, self.metric = d, K, kind, int(nbits), metric
-        self.coarse: Optional[torch.Tensor] = None
+        super().__init__(d, K, metric)
+        self.kind, self.nbits = kind, int(nbits)
         self.params: Optional[Tuple[torch.Tensor, ...]] = None
-        self.lists: Optional[IvfLists] = None
         self.pos: Optional[torch.Tensor] = None
-        self.ntotal = 0
-
-    def train(self, X: torch.Tensor, coarse_iters: int = 10, seed: int = 1234) -> None:
-        self.coarse = train_coarse(X, self.K, niter=coarse_iters, seed=seed, metric=self.metric)
-
-    def _assign(self, X: torch.Tensor) -> torch.Tensor:
-        n = X.shape[0]
-        a = torch.empty(n, dtype=torch.int32, device=X.device)
-        step = _rows_per_chunk(self.K)
-        for s in range(0, n, step):
-            e = min(n, s + step)
-            _, a[s:e] = assign(X[s:e], self.coarse, self.metric)
-        return a
 
     def _lvq_means(self, X: torch.Tensor, a: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor) -> torch.Tensor:
         """mu (K, d): the ascending-row f32 mean of every list's residuals (0 for an empty list):
@@ -326,27 +300,18 @@ class IvfCodes:
     def fit_lists(self, X: torch.Tensor) -> None:
         """Assign every row, fit each list's quantizer on its residuals, encode, and lay the
         lists out in bucket order (ids 0 .. N - 1)."""
-        n = X.shape[0]
         a = self._assign(X)
         offsets, order = _native.bucket_sort(a, self.K)
         self.params = tuple(self._fit_params(X, a, offsets, order))
-        codes = self._encode(X, a)
-        row_bytes = codes.shape[1] * codes.element_size()
-        self.lists = IvfLists(
-            offsets=offsets,
-            codes=_native.gather_rows(codes, order) if row_bytes % 4 == 0 else codes[order.long()].contiguous(),
-            ids=order.clone(),
-            tau=None,
-        )
-        self.ntotal = n
+        self.lists = IvfLists(offsets=offsets, codes=self._gather(self._encode(X, a), order), ids=order.clone(), tau=None)
+        self.ntotal = X.shape[0]
         self._index_rows()
 
     def _index_rows(self) -> None:
         ids = self.lists.ids.long() & 0xFFFFFFFF
         self.pos = torch.empty(ids.numel(), dtype=torch.int64, device=ids.device)
         self.pos[ids] = torch.arange(ids.numel(), dtype=torch.int64, device=ids.device)
-        self.list_of = torch.repeat_interleave(torch.arange(self.K, dtype=torch.int32, device=ids.device),
-                                               self.lists.offsets[1:] - self.lists.offsets[:-1]).contiguous()
+        self.list_of = self._list_of().contiguous()
 
     def reconstruct(self, rows: torch.Tensor) -> torch.Tensor:
         """x^ (len(rows), d) f32 of the rows with these ids, through the decode entry points."""
@@ -358,14 +323,8 @@ class IvfCodes:
             return _native.ivf_sq_decode(codes, self.coarse, a, lo, den, self.nbits)
         return _native.ivf_lvq_decode(codes, self.coarse, a, self.params[0], self.nbits)
 
-    def probes(self, Q: torch.Tensor, nprobe: int) -> torch.Tensor:
-        nprobe = max(1, min(int(nprobe), self.K))
-        if nprobe > 256:
-            raise ValueError(f"nprobe={nprobe}: the probe selection (mivq_topk_rows) supports at most 256 lists")
-        return _native.topk_rows(_native.pairwise_distances(Q, self.coarse, self.metric), nprobe)[1]
-
     def search(self, Q: torch.Tensor, k: int, nprobe: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """(keys f32 (nq, k), ids int32 (nq, k)); L2 ascending, IP as negated inner products."""
         L = self.lists
-        return _native.ivf_code_search(self.kind, Q, self.coarse, self.probes(Q, nprobe), L.offsets, L.codes, L.ids,
-                                       self.params, self.nbits, self.metric, k)
+        return _native.ivf_code_search(self.kind, Q, self.coarse, self.probes(Q, nprobe), L.offsets, L.codes,
+                                       L.ids, self.params, self.nbits, self.metric, k)
