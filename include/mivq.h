@@ -206,6 +206,41 @@ int mivq_extrabitq_finish(const double* y, int64_t n, int32_t d, const uint8_t* 
 int mivq_extrabitq_rotate(const double* o, int64_t n, int32_t d, const double* P, int32_t transpose,
                           double* s, void* stream);
 
+/* ------------------------------------------------------ Rank-aware quantizer (PCA + bits per dimension)
+ * The per-row steps of RankAwareQuantizer.compress / decompress (rank_aware_quantization.py),
+ * fp64 like the reference; the two D x D products between them (xc . V, y_hat . V^T) are
+ * mivq_extrabitq_rotate.  The code format is four device tables:
+ *   lv     (T,)    f64    the level tables of all dimensions, concatenated (ascending within a
+ *                         dimension; a 0-bit dimension has its one level)
+ *   lv_off (d + 1,) int32 start of dimension j's 2^width[j] levels in lv
+ *   width  (d,)    int32  bits of dimension j, 0..8
+ *   pos    (d,)    int32  bit position of the most significant bit of j's field in the code row,
+ *                         counted MSB-first from the start of the row (bit p is bit 7 - p % 8 of
+ *                         byte p / 8); ignored where width is 0.  Fields do not overlap and
+ *                         pos + width <= 8 * code_size (the caller's duty; a field that breaks
+ *                         this, or a width outside 0..8, is treated as width 0).
+ *   center    : xc = (double)x - mu                          x (n, d) f32 or f64, mu (d,) f64
+ *   quantize  : idx_j = #{ q : 0.5 (L[q] + L[q+1]) < y_j },  L = lv + lv_off[j]
+ *               (np.searchsorted, side left: a y on a mid-level takes the lower index, -inf
+ *               gives 0, +inf and NaN give 2^w - 1); codes (n, code_size): idx_j in width[j]
+ *               bits, MSB first, from bit pos[j]; every bit of no field is 0
+ *   dequantize: y_hat_j = L[idx_j], idx_j the width[j] bits at pos[j] (0 for width 0); bits of
+ *               no field are ignored, and no byte pattern indexes outside a dimension's levels
+ *   finish    : out = (float)(z + mu)                        z (n, d) f64, out (n, d) f32
+ * n < 0, d <= 0, code_size <= 0 or a null pointer with n > 0 return MIVQ_ERR_INVALID before any
+ * launch; n == 0 returns MIVQ_OK without one; code_size above 48000 bytes (quantize, dequantize: the rows' codes
+ * are held in LDS) is MIVQ_ERR_UNSUPPORTED. */
+int mivq_rankaware_center(const void* x, int32_t x_is_f64, int64_t n, int32_t d, const double* mu,
+                          double* xc, void* stream);
+int mivq_rankaware_quantize(const double* y, int64_t n, int32_t d, const double* lv,
+                            const int32_t* lv_off, const int32_t* pos, const int32_t* width,
+                            int32_t code_size, uint8_t* codes, void* stream);
+int mivq_rankaware_dequantize(const uint8_t* codes, int64_t n, int32_t d, const double* lv,
+                              const int32_t* lv_off, const int32_t* pos, const int32_t* width,
+                              int32_t code_size, double* y_hat, void* stream);
+int mivq_rankaware_finish(const double* z, int64_t n, int32_t d, const double* mu, float* out,
+                          void* stream);
+
 /* ------------------------------------------------------ ADC search
  * Flat asymmetric-distance search over PQ codes; the GPU counterpart of
  * FlatQuantizedIndex.search_with_scores (methods/search/flat_quantized_index.py:45-76),

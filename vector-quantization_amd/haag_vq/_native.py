@@ -18,7 +18,7 @@ import ctypes
 import os
 import threading
 from pathlib import Path
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch  # noqa: F401  (must be imported before libmivq: they share libamdhip64.so.7)
 
@@ -78,6 +78,10 @@ SIGNATURES = {
     "mivq_extrabitq_dequantize": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp]),
     "mivq_extrabitq_finish": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp]),
     "mivq_extrabitq_rotate": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp]),
+    "mivq_rankaware_center": (_c.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _vp]),
+    "mivq_rankaware_quantize": (_c.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "mivq_rankaware_dequantize": (_c.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "mivq_rankaware_finish": (_c.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
     "mivq_adc_lut": (_c.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
     "mivq_adc_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
     "mivq_adc_search": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _sz, _vp, _vp, _c.c_uint32,
@@ -576,6 +580,151 @@ def extrabitq_decode(codes: torch.Tensor, c: torch.Tensor, P: torch.Tensor, leve
     out = torch.empty((n, d), dtype=torch.float32, device=codes.device)
     _call("mivq_extrabitq_finish", _ptr(y), n, d, _ptr(codes), nbits, _ptr(c), _ptr(out), _stream())
     return out
+
+
+# ----------------------------------------------------------------- rank-aware quantizer
+class RankAwareState(NamedTuple):
+    """The device side of a fitted RankAwareQuantizer: mu (d,) f64, V (d, d) f64 and the four
+    format tables of include/mivq.h (lv f64, lv_off / pos / width int32)."""
+    mu: torch.Tensor
+    V: torch.Tensor
+    lv: torch.Tensor
+    lv_off: torch.Tensor
+    pos: torch.Tensor
+    width: torch.Tensor
+    code_size: int
+
+
+def rankaware_tables(cb, bits, pos, code_size: int):
+    """Host arrays (lv f64, lv_off, pos, width int32) of a per-dimension codebook list `cb`,
+    widths `bits` and field positions `pos`, checked: widths in [0, 8], 2^width levels per
+    dimension, every field inside the row, no two fields on one bit."""
+    import numpy as np
+
+    width = np.asarray(bits, dtype=np.int64)
+    pos = np.asarray(pos, dtype=np.int64)
+    d = width.shape[0]
+    code_size = int(code_size)
+    if width.ndim != 1 or d < 1 or pos.shape != (d,) or len(cb) != d:
+        raise ValueError(f"rankaware: {len(cb)} codebooks, widths {width.shape} and positions {pos.shape} differ")
+    if code_size < 1:
+        raise ValueError(f"rankaware: code_size must be positive, got {code_size}")
+    if np.any(width < 0) or np.any(width > 8):
+        raise ValueError("rankaware: widths must be in [0, 8]")
+    sizes = np.array([np.asarray(c).shape[0] for c in cb], dtype=np.int64)
+    if np.any(sizes != 2 ** width):
+        j = int(np.flatnonzero(sizes != 2 ** width)[0])
+        raise ValueError(f"rankaware: dimension {j} has {sizes[j]} levels for {width[j]} bits")
+    on = width > 0
+    pos = np.where(on, pos, 0)
+    if np.any(pos < 0) or np.any(pos + width > 8 * code_size):
+        raise ValueError(f"rankaware: a field lies outside the {code_size}-byte row")
+    used = np.zeros(8 * code_size + 1, dtype=np.int64)
+    np.add.at(used, pos[on], 1)
+    np.add.at(used, (pos + width)[on], -1)
+    if np.any(np.cumsum(used) > 1):
+        raise ValueError("rankaware: fields overlap")
+    lv_off = np.concatenate(([0], np.cumsum(sizes)))
+    if lv_off[-1] >= 2 ** 31:
+        raise ValueError("rankaware: level tables too large")
+    lv = np.concatenate([np.asarray(c, dtype=np.float64) for c in cb])
+    return lv, lv_off.astype(np.int32), pos.astype(np.int32), width.astype(np.int32)
+
+
+def rankaware_state(mu, V, cb, bits, pos, code_size: int, device: Optional[torch.device] = None) -> RankAwareState:
+    """Check the format (rankaware_tables) and put the model on the device."""
+    import numpy as np
+
+    lv, lv_off, pos, width = rankaware_tables(cb, bits, pos, code_size)
+    d = width.shape[0]
+    mu = np.ascontiguousarray(mu, dtype=np.float64)
+    V = np.ascontiguousarray(V, dtype=np.float64)
+    if mu.shape != (d,) or V.shape != (d, d):
+        raise ValueError(f"rankaware: mu {mu.shape} / V {V.shape} do not match d={d}")
+    dev = device if device is not None else require_device()
+    return RankAwareState(*(torch.from_numpy(a).to(dev) for a in (mu, V, lv, lv_off, pos, width)), int(code_size))
+
+
+def _rankaware_check(st: RankAwareState) -> int:
+    _check(st.mu, "mu", torch.float64, 1)
+    _check(st.V, "V", torch.float64, 2)
+    _check(st.lv, "lv", torch.float64, 1)
+    d = st.mu.numel()
+    for t, nm, ln in ((st.lv_off, "lv_off", d + 1), (st.pos, "pos", d), (st.width, "width", d)):
+        _check(t, nm, torch.int32, 1)
+        if t.numel() != ln:
+            raise ValueError(f"rankaware: {nm} has {t.numel()} entries, expected {ln}")
+    if tuple(st.V.shape) != (d, d):
+        raise ValueError(f"rankaware: V shape {tuple(st.V.shape)} != {(d, d)}")
+    return d
+
+
+def rankaware_center(x: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
+    """(double)x - mu, (n, d) f64, for f32 or f64 rows."""
+    if x.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"rankaware: unsupported dtype {x.dtype}")
+    _check(x, "x", x.dtype, 2)
+    _check(mu, "mu", torch.float64, 1)
+    n, d = x.shape
+    if mu.numel() != d:
+        raise ValueError(f"rankaware_center: mu has {mu.numel()} entries, data has d={d}")
+    xc = torch.empty((n, d), dtype=torch.float64, device=x.device)
+    _call("mivq_rankaware_center", _ptr(x), 1 if x.dtype == torch.float64 else 0, n, d, _ptr(mu), _ptr(xc), _stream())
+    return xc
+
+
+def rankaware_quantize(y: torch.Tensor, st: RankAwareState, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Code rows (n, code_size) u8 of the rotated rows y (n, d) f64."""
+    d = _rankaware_check(st)
+    _check(y, "y", torch.float64, 2)
+    if y.shape[1] != d:
+        raise ValueError(f"rankaware_quantize: y has d={y.shape[1]}, the state d={d}")
+    n = y.shape[0]
+    if out is None:
+        codes = torch.empty((n, st.code_size), dtype=torch.uint8, device=y.device)
+    else:
+        _check(out, "out", torch.uint8, 2)
+        if tuple(out.shape) != (n, st.code_size):
+            raise ValueError(f"out shape {tuple(out.shape)} != {(n, st.code_size)}")
+        codes = out
+    _call("mivq_rankaware_quantize", _ptr(y), n, d, _ptr(st.lv), _ptr(st.lv_off), _ptr(st.pos), _ptr(st.width),
+          st.code_size, _ptr(codes), _stream())
+    return codes
+
+
+def rankaware_dequantize(codes: torch.Tensor, st: RankAwareState) -> torch.Tensor:
+    """The levels (n, d) f64 the code rows name."""
+    d = _rankaware_check(st)
+    _check(codes, "codes", torch.uint8, 2)
+    if codes.shape[1] != st.code_size:
+        raise ValueError(f"codes have {codes.shape[1]} bytes per row, expected {st.code_size}")
+    n = codes.shape[0]
+    y_hat = torch.empty((n, d), dtype=torch.float64, device=codes.device)
+    _call("mivq_rankaware_dequantize", _ptr(codes), n, d, _ptr(st.lv), _ptr(st.lv_off), _ptr(st.pos), _ptr(st.width),
+          st.code_size, _ptr(y_hat), _stream())
+    return y_hat
+
+
+def rankaware_finish(z: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
+    """(float)(z + mu), (n, d) f32."""
+    _check(z, "z", torch.float64, 2)
+    _check(mu, "mu", torch.float64, 1)
+    n, d = z.shape
+    if mu.numel() != d:
+        raise ValueError(f"rankaware_finish: mu has {mu.numel()} entries, data has d={d}")
+    out = torch.empty((n, d), dtype=torch.float32, device=z.device)
+    _call("mivq_rankaware_finish", _ptr(z), n, d, _ptr(mu), _ptr(out), _stream())
+    return out
+
+
+def rankaware_encode(x: torch.Tensor, st: RankAwareState) -> torch.Tensor:
+    """Codes of RankAwareQuantizer.compress: center, (x - mu) . V on mivq_extrabitq_rotate, quantize."""
+    return rankaware_quantize(extrabitq_rotate(rankaware_center(x, st.mu), st.V, False), st)
+
+
+def rankaware_decode(codes: torch.Tensor, st: RankAwareState) -> torch.Tensor:
+    """RankAwareQuantizer.decompress: dequantize, y_hat . V^T on mivq_extrabitq_rotate, finish."""
+    return rankaware_finish(extrabitq_rotate(rankaware_dequantize(codes, st), st.V, True), st.mu)
 
 
 # ----------------------------------------------------------------- ADC / flat search

@@ -3,7 +3,7 @@
 from .base_quantizer import BaseQuantizer
 from .base_search_index import BaseSearchIndex
 
-__all__ = ["BaseQuantizer", "BaseSearchIndex", "IvfQuantizedIndex"]
+__all__ = ["BaseQuantizer", "BaseSearchIndex", "IvfQuantizedIndex", "RankAwareQuantizer"]
 
 
 def __getattr__(name):
@@ -12,4 +12,8 @@ def __getattr__(name):
         from .search.ivf_quantized_index import IvfQuantizedIndex
 
         return IvfQuantizedIndex
+    if name == "RankAwareQuantizer":
+        from .rank_aware_quantization import RankAwareQuantizer
+
+        return RankAwareQuantizer
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

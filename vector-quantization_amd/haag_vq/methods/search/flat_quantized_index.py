@@ -39,6 +39,7 @@ from ..lvq_quantization import LVQQuantizer
 from ..optimized_product_quantization import OptimizedProductQuantizer, OPQHandle
 from ..product_quantization import ProductQuantizer
 from ..rabit_quantization import RaBitQuantizer
+from ..rank_aware_quantization import RankAwareQuantizer
 from ..scalar_quantization import ScalarQuantizer
 
 _METRIC = {"l2": _native.METRIC_L2, "ip": _native.METRIC_INNER_PRODUCT}
@@ -134,6 +135,15 @@ def quantizer_state(q: BaseQuantizer) -> dict:
         return dict(qtype=np.array("rabitq"), metric_type=np.array(int(q.metric_type)), d=np.array(q.rabitq.d))
     if isinstance(q, LVQQuantizer):
         return dict(qtype=np.array("lvq"), num_bits=np.array(q.num_bits), mu=np.asarray(q.mu, dtype=np.float32))
+    if isinstance(q, RankAwareQuantizer):
+        if q.V is None:
+            raise ValueError("save(): the RankAwareQuantizer is not fitted")
+        return dict(qtype=np.array("rankaware"), avg_bits=np.array(q.avg_bits), alpha=np.array(q.alpha),
+                    max_bits=np.array(q.max_bits), seed=np.array(q.seed), packing=np.array(q.packing),
+                    mu=np.asarray(q.mu, dtype=np.float64), V=np.ascontiguousarray(q.V, dtype=np.float64),
+                    var=np.asarray(q.var, dtype=np.float64), bits=np.asarray(q.bits, dtype=np.int64),
+                    cb=np.concatenate(q.cb).astype(np.float64), levels=np.concatenate(q._levels).astype(np.float64),
+                    Dg=np.asarray(q._Dg, dtype=np.float64))
     raise ValueError(f"save(): unsupported quantizer {type(q).__name__}")
 
 
@@ -161,6 +171,21 @@ def quantizer_from_state(z) -> BaseQuantizer:
     elif qt == "lvq":
         q = LVQQuantizer(num_bits=int(z["num_bits"]))
         q.mu = np.array(z["mu"])
+    elif qt == "rankaware":
+        q = RankAwareQuantizer(avg_bits=float(z["avg_bits"]), alpha=float(z["alpha"]), max_bits=int(z["max_bits"]),
+                               seed=int(z["seed"]), packing=str(z["packing"]))
+        q.mu, q.V, q.var = np.array(z["mu"]), np.array(z["V"]), np.array(z["var"])
+        q.bits = np.array(z["bits"], dtype=np.int64)
+        q.D = int(q.bits.shape[0])
+        ends = np.cumsum(2 ** q.bits)
+        cb = np.array(z["cb"], dtype=np.float64)
+        if cb.shape != (int(ends[-1]),) or q.V.shape != (q.D, q.D) or q.mu.shape != (q.D,):
+            raise ValueError("load(): inconsistent rank-aware quantizer state")
+        q.cb = [cb[e - 2 ** b:e] for e, b in zip(ends, q.bits)]
+        lv = np.array(z["levels"], dtype=np.float64)
+        q._levels = [lv[2 ** b - 1:2 ** (b + 1) - 1] for b in range(q.max_bits + 1)]
+        q._Dg = np.array(z["Dg"])
+        q._layout()
     else:
         raise ValueError(f"load(): unknown quantizer type {qt!r}")
     return q
