@@ -177,6 +177,48 @@ def test_extrabitq_rotate_matches_fp64(dev, n, d, transpose):
     assert np.all(np.abs(got - ref) <= 1e-14 * d * scale + 1e-300), float(np.max(np.abs(got - ref) / scale))
 
 
+@pytest.mark.parametrize("n,d", [(1, 16), (5, 32), (130, 100), (129, 160), (77, 200)])
+@pytest.mark.parametrize("transpose", [False, True])
+def test_gemm_f64_integer_exact(dev, n, d, transpose):
+    """gemm_f64 on integer-valued fp64 operands, |v| <= 2^10: with d <= 3072 every product and
+    partial sum is an integer below 2^32, exact in any summation order, so the result equals the
+    int64 product exactly.  (1, 16): generic kernel, one slice; (5, 32): fast kernel, two slices
+    (its look-ahead loads all past d); (130, 100): generic, two row tiles, ragged d; (129, 160):
+    fast, second column tile 32 wide; (77, 200): generic, ragged second column tile, odd slice
+    count."""
+    from haag_vq import _native
+
+    rng = np.random.default_rng(n * 11 + d)
+    o = rng.integers(-1024, 1025, (n, d))
+    P = rng.integers(-1024, 1025, (d, d))
+    got = _h(_native.gemm_f64(_t(o.astype(np.float64), dev), _t(P.astype(np.float64), dev), transpose))
+    ref = o @ (P.T if transpose else P)
+    np.testing.assert_array_equal(got, ref.astype(np.float64))
+
+
+@pytest.mark.parametrize("d,dp", [(16, 32), (100, 128), (200, 224)])
+@pytest.mark.parametrize("transpose", [False, True])
+def test_gemm_f64_generic_and_fast_kernels_agree(dev, d, dp, transpose):
+    """The generic kernel at d against the d % 32 == 0 kernel on the same operands zero-padded
+    to dp columns (the same column-tile count): bit for bit.  The appended terms are +0 products
+    added to accumulators that are never -0, so equal results mean the same tile, slices and
+    MFMA order in both kernels."""
+    from haag_vq import _native
+
+    n = 77
+    rng = np.random.default_rng(n * 7 + d)
+    o = rng.standard_normal((n, d))
+    P, _ = np.linalg.qr(rng.standard_normal((d, d)))
+    op = np.zeros((n, dp))
+    op[:, :d] = o
+    Pp = np.zeros((dp, dp))
+    Pp[:d, :d] = P
+    small = _h(_native.gemm_f64(_t(o, dev), _t(P, dev), transpose))
+    padded = _h(_native.gemm_f64(_t(op, dev), _t(Pp, dev), transpose))
+    np.testing.assert_array_equal(padded[:, :d], small)
+    np.testing.assert_array_equal(padded[:, d:], 0.0)
+
+
 def _prep_offsets(M, dsub, ksub=256):
     """Byte offsets inside the mivq_pq_prepare buffer (mirror of PqPrepLayout, mivq_common.h)."""
     al = lambda v: (v + 255) // 256 * 256  # noqa: E731

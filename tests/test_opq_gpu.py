@@ -172,6 +172,39 @@ def test_opq_gram_matches_fp64(dev, n, d):
     assert np.all(np.abs(G - ref) <= bound * max(1, n) ** 0.5 + 0)
 
 
+@pytest.mark.parametrize("n,d", [(0, 64), (1, 16), (33, 200), (130, 100), (4100, 130)])
+def test_opq_gram_integer_exact(dev, n, d):
+    """mivq_opq_gram on integer-valued f32 rows, |v| <= 2^10: the sums stay below 2^37, exact
+    through the split and the ordered reduce, so G equals the int64 X^T Y exactly.  (0, 64): the
+    memset path; (33, 200): four tiles, one split, ragged last K step; (130, 100): three splits
+    of 44 / 44 / 42 rows; (4100, 130): 64 splits of 65 rows, the last with 5."""
+    from haag_vq import _native
+
+    rng = np.random.default_rng(n * 3 + d)
+    X = rng.integers(-1024, 1025, (n, d))
+    Y = rng.integers(-1024, 1025, (n, d))
+    G = _native.opq_gram(_t(X.astype(np.float32), dev), _t(Y.astype(np.float32), dev)).cpu().numpy()
+    np.testing.assert_array_equal(G, (X.T @ Y).astype(np.float64))
+
+
+def test_opq_gram_column_padding(dev):
+    """Gaussian (130, 100) rows against the same rows zero-padded to 128 columns (the same tile
+    and splits): the common block of G is the same bit for bit."""
+    from haag_vq import _native
+
+    n, d, dp = 130, 100, 128
+    rng = np.random.default_rng(n + d)
+    X = np.zeros((n, dp), dtype=np.float32)
+    Y = np.zeros((n, dp), dtype=np.float32)
+    X[:, :d] = rng.standard_normal((n, d))
+    Y[:, :d] = rng.standard_normal((n, d)) * rng.uniform(0.01, 100, d)
+    G = _native.opq_gram(_t(X[:, :d], dev), _t(Y[:, :d], dev)).cpu().numpy()
+    Gp = _native.opq_gram(_t(X, dev), _t(Y, dev)).cpu().numpy()
+    np.testing.assert_array_equal(Gp[:d, :d], G)
+    np.testing.assert_array_equal(Gp[d:], 0.0)
+    np.testing.assert_array_equal(Gp[:, d:], 0.0)
+
+
 def test_polar_factor_newton_schulz(dev):
     """polar_factor: the orthogonal polar factor U V^T of an ill-conditioned G (kappa ~ 1e4)
     from the Newton-Schulz iteration on the fp64 MFMA GEMM, vs numpy's SVD; a rank-deficient

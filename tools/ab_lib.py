@@ -1,9 +1,10 @@
 """Interleaved A/B of one entry point between two builds of libmivq.so (same process, same data).
 
-usage: python tools/ab_lib.py OTHER.so [--what encode|adc|lut|flat|sq|rabitq|lvq|pairwise|ivf_rabitq|ivf_sq|ivf_lvq]
+usage: python tools/ab_lib.py OTHER.so [--what encode|adc|lut|flat|sq|rabitq|lvq|pairwise|ivf_rabitq|ivf_sq|ivf_lvq|
+                                              gemm_f64|gram]
                               [--n 1000000] [--d 1536] [--M 16] [--data gaussian] [--reps 10]
                               [--nq 1000] [--k 10] [--metric l2|ip] [--nbits 8] [--this THIS.so]
-                              [--nlist 1024] [--nprobe 16] [--qb 4]
+                              [--nlist 1024] [--nprobe 16] [--qb 4] [--transpose]
 The in-tree library (vector-quantization_amd/lib/libmivq.so) is "this"; OTHER.so is e.g. a
 build of the previous commit (git stash; make; cp lib/libmivq.so /tmp/old.so; git stash pop).
 --this names another build in its place (the same file as OTHER.so: an A/A pass, the noise floor
@@ -19,6 +20,9 @@ checks that both builds give identical outputs:
   ivf_rabitq, ivf_sq, ivf_lvq   the searches over probed lists mivq_ivf_rabitq_search (--qb),
             mivq_ivf_sq_search, mivq_ivf_lvq_search (--nbits): seeded random code rows in --nlist lists
             of seeded uneven sizes, --nprobe random distinct lists per query, no training; ids and keys
+  gemm_f64  mivq_extrabitq_rotate (the fp64 GEMM of csrc/gemm_f64.hip): a seeded Gaussian (n, d) o times a
+            QR factor P, or P^T with --transpose; the product, and the fp64 MFMA rate (2 n d^2 FLOP per call)
+  gram      mivq_opq_gram: seeded Gaussian f32 X and Y (Y with per-column scales 0.01 .. 100), the Gram matrix
 """
 import argparse
 import ctypes
@@ -93,6 +97,7 @@ EXACT = {
 
 
 IVF = ("ivf_rabitq", "ivf_sq", "ivf_lvq")
+GEMM = ("gemm_f64", "gram")
 
 
 def exact_leg(a, libs, dev, st):
@@ -167,6 +172,34 @@ def ivf_leg(a, libs, dev, st):
     return run, lambda k: bufs[k][1:]
 
 
+def gemm_leg(a, libs, dev, st):
+    """run(k) and outputs() of the fp64 GEMM (mivq_extrabitq_rotate) or of mivq_opq_gram."""
+    g = torch.Generator(device=dev).manual_seed(5)
+    if a.what == "gemm_f64":
+        o = torch.randn((a.n, a.d), dtype=torch.float64, device=dev, generator=g)
+        Pm = torch.linalg.qr(torch.randn((a.d, a.d), dtype=torch.float64, device=dev, generator=g))[0].contiguous()
+        out = {k: torch.empty((a.n, a.d), dtype=torch.float64, device=dev) for k in libs}
+
+        def run(k):
+            rc = libs[k].mivq_extrabitq_rotate(_ptr(o), a.n, a.d, _ptr(Pm), int(a.transpose), _ptr(out[k]), P(st))
+            assert rc == 0, (rc, libs[k].mivq_last_error())
+
+        return run, lambda k: (out[k],)
+    X = torch.randn((a.n, a.d), device=dev, generator=g)
+    Y = torch.randn((a.n, a.d), device=dev, generator=g) * (torch.rand(a.d, device=dev, generator=g) * 99.99 + 0.01)
+    bufs = {}
+    for k, lb in libs.items():
+        ws = torch.empty(max(lb.mivq_opq_gram_workspace_bytes(a.n, a.d), 256), dtype=torch.uint8, device=dev)
+        bufs[k] = (ws, torch.empty((a.d, a.d), dtype=torch.float64, device=dev))
+
+    def run(k):
+        ws, G = bufs[k]
+        rc = libs[k].mivq_opq_gram(_ptr(X), _ptr(Y), a.n, a.d, _ptr(ws), ws.numel(), _ptr(G), P(st))
+        assert rc == 0, (rc, libs[k].mivq_last_error())
+
+    return run, lambda k: (bufs[k][1],)
+
+
 def pq_leg(a, libs, dev, st):
     """run(k) and outputs() of mivq_pq_encode, mivq_adc_lut or mivq_adc_search."""
     X = synth(a.n, a.d, 0, dev, kind=a.data)
@@ -228,7 +261,7 @@ def main():
     ap.add_argument("--M", type=int, default=16)
     ap.add_argument("--data", default="gaussian")
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--what", choices=("encode", "adc", "lut", "pairwise", *EXACT, *IVF), default="encode")
+    ap.add_argument("--what", choices=("encode", "adc", "lut", "pairwise", *EXACT, *IVF, *GEMM), default="encode")
     ap.add_argument("--nq", type=int, default=1000)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--metric", choices=("l2", "ip"), default="l2")
@@ -236,11 +269,13 @@ def main():
     ap.add_argument("--nlist", type=int, default=1024)
     ap.add_argument("--nprobe", type=int, default=16)
     ap.add_argument("--qb", type=int, default=4)
+    ap.add_argument("--transpose", action="store_true")
     a = ap.parse_args()
     dev = _native.require_device()
     libs = {k: bind(p if Path(p).is_absolute() else ROOT / p) for k, p in (("this", a.this), ("other", a.other))}
     st = torch.cuda.current_stream().cuda_stream
-    leg = pq_leg if a.what in ("encode", "adc", "lut") else ivf_leg if a.what in IVF else exact_leg
+    leg = (pq_leg if a.what in ("encode", "adc", "lut") else ivf_leg if a.what in IVF
+           else gemm_leg if a.what in GEMM else exact_leg)
     run, outputs = leg(a, libs, dev, st)
     for k in libs:
         run(k)
@@ -271,6 +306,9 @@ def main():
             if a.what == "encode":
                 gbs = a.n * (4 * a.d + a.M) / (ms * 1e-3) / 1e9
                 print(f"AB {k} round {rnd}: back-to-back {ms:.3f} ms/call = {gbs / 8000:.3f} of 8 TB/s", flush=True)
+            elif a.what in GEMM:
+                tf = 2.0 * a.n * a.d * a.d / (ms * 1e-3) / 1e12
+                print(f"AB {k} round {rnd}: back-to-back {ms:.3f} ms/call = {tf:.1f} TF/s", flush=True)
             else:
                 print(f"AB {k} round {rnd}: back-to-back {ms:.3f} ms/call = {a.nq / ms * 1e3:.0f} queries/s", flush=True)
     if not same:

@@ -108,13 +108,13 @@ def main() -> int:
             print(f"    compress    rankaware {ms(tc)}   extrabitq {ms(te)}   ratio {tc[0] / te[0]:.3f}")
             print(f"    decompress  rankaware {ms(td)}   extrabitq {ms(tf)}   ratio {td[0] / tf[0]:.3f}")
             xc = _native.rankaware_center(X, st.mu)
-            y = _native.extrabitq_rotate(xc, st.V, False)
+            y = _native.gemm_f64(xc, st.V, False)
             yh = _native.rankaware_dequantize(codes, st)
-            zz = _native.extrabitq_rotate(yh, st.V, True)
-            s = alternate([lambda: _native.rankaware_center(X, st.mu), lambda: _native.extrabitq_rotate(xc, st.V, False),
+            zz = _native.gemm_f64(yh, st.V, True)
+            s = alternate([lambda: _native.rankaware_center(X, st.mu), lambda: _native.gemm_f64(xc, st.V, False),
                            lambda: _native.rankaware_quantize(y, st, out=codes),
                            lambda: _native.rankaware_dequantize(codes, st),
-                           lambda: _native.extrabitq_rotate(yh, st.V, True), lambda: _native.rankaware_finish(zz, st.mu)],
+                           lambda: _native.gemm_f64(yh, st.V, True), lambda: _native.rankaware_finish(zz, st.mu)],
                           a.reps, a.min_seconds)
             qb = 8 * n * d + n * cs
             fl = 2.0 * n * d * d

@@ -29,6 +29,7 @@
 //    beside (its own, torch's), so every shape takes the register-staged path.
 // 2. opq_gemm_kernel (mivq_opq_rotate, no preparation, any d): plain fp32 MFMA
 //    (v_mfma_f32_32x32x2_f32), 128 x 128 tiles, BK = 16 slices staged through LDS.
+// The fp64 kernels of the OPQ fit (mivq_opq_gram, the polar factor's GEMM) are in gemm_f64.hip.
 #include <math.h>
 
 #include <algorithm>
@@ -413,115 +414,6 @@ __global__ __launch_bounds__(WR * WC * 64) void opq_split_gemm_kernel(const floa
     store_tile<RB, CB>(acc, smem, w, l, r0 + wr * RB * 32, c0 + wc * CB * 32, n, d, rs, hdr[1], y);
 }
 
-// ------------------------------------------------------------ Procrustes Gram matrix (training)
-// G = X^T Y in fp64 for the OPQ update (faiss OPQMatrix::train's X^T Yhat before its SVD,
-// /root/reference/src/haag_vq/methods/optimized_product_quantization.py:21-28): X, Y (n, d) f32
-// rows, each product exact in fp64 (24 + 24 bits), sums in fp64 on v_mfma_f64_16x16x4_f64.
-// Split K: workgroup (tile, s) sums rows [s R, (s + 1) R) of a 128 x 128 tile of G into
-// part[s]; opq_gram_reduce_kernel adds the parts in s order (deterministic).  4 waves of 64 x 64
-// (4 x 4 blocks); f64 operand map as erq_rotate_kernel: A[l & 15][l >> 4], B[l >> 4][l & 15],
-// D column l & 15, rows (l >> 4) + 4 g.
-constexpr int GR_T = 128, GR_K = 16, GR_P = GR_T + 2;  // LDS rows of 130 doubles: [k][i]
-typedef double f64x4g __attribute__((ext_vector_type(4)));
-
-__global__ __launch_bounds__(256) void opq_gram_kernel(const float* __restrict__ X, const float* __restrict__ Y,
-                                                         int64_t n, int d, int64_t rows_per_split, int ctiles,
-                                                         double* __restrict__ part) {
-    __shared__ double As[2][GR_K * GR_P];
-    __shared__ double Bs[2][GR_K * GR_P];
-    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
-    const int wr = w >> 1, wc = w & 1;
-    const int tile = blockIdx.x, sp = blockIdx.y;
-    const int i0 = (tile / ctiles) * GR_T, j0 = (tile % ctiles) * GR_T;
-    const int64_t ra = (int64_t)sp * rows_per_split;
-    const int64_t rb = min(n, ra + rows_per_split);
-    f64x4g acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = (f64x4g){0.0, 0.0, 0.0, 0.0};
-    // staging: thread t loads rows k = t >> 4 of the 16-row step, columns 8 (t & 15) .. +7 of the
-    // tile (two float4 of X, two of Y); out-of-range rows / columns read as 0
-    const int kr = tid >> 4, cc = 8 * (tid & 15);
-    float xa[8], yb[8];
-    auto gload = [&](int64_t r) __attribute__((always_inline)) {
-        const int64_t row = r + kr;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int ci = i0 + cc + u, cj = j0 + cc + u;
-            xa[u] = (row < rb && ci < d) ? X[row * d + ci] : 0.0f;
-            yb[u] = (row < rb && cj < d) ? Y[row * d + cj] : 0.0f;
-        }
-    };
-    auto sstore = [&](int st) __attribute__((always_inline)) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            As[st][kr * GR_P + cc + u] = (double)xa[u];
-            Bs[st][kr * GR_P + cc + u] = (double)yb[u];
-        }
-    };
-    const int64_t nk = (rb - ra + GR_K - 1) / GR_K;
-    if (nk <= 0) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int i = i0 + wr * 64 + a * 16 + (l >> 4) + 4 * g, j = j0 + wc * 64 + b * 16 + (l & 15);
-                    if (i < d && j < d) part[((int64_t)sp * d + i) * d + j] = 0.0;
-                }
-        return;
-    }
-    gload(ra);
-    sstore(0);
-    __syncthreads();
-    const int fi = l & 15, fk = l >> 4;
-    for (int64_t ks = 0; ks < nk; ++ks) {
-        const int st = (int)(ks & 1);
-        if (ks + 1 < nk) gload(ra + (ks + 1) * GR_K);
-#pragma unroll
-        for (int k4 = 0; k4 < GR_K; k4 += 4) {
-            double af[4], bf[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) af[a] = As[st][(k4 + fk) * GR_P + wr * 64 + a * 16 + fi];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) bf[b] = Bs[st][(k4 + fk) * GR_P + wc * 64 + b * 16 + fi];
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf[b], acc[a][b], 0, 0, 0);
-        }
-        if (ks + 1 < nk) sstore(st ^ 1);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int i = i0 + wr * 64 + a * 16 + fk + 4 * g, j = j0 + wc * 64 + b * 16 + fi;
-                if (i < d && j < d) part[((int64_t)sp * d + i) * d + j] = acc[a][b][g];
-            }
-}
-
-__global__ __launch_bounds__(256) void opq_gram_reduce_kernel(const double* __restrict__ part, int splits, int64_t dd,
-                                                                double* __restrict__ G) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= dd) return;
-    double s = part[e];
-    for (int p = 1; p < splits; ++p) s += part[(int64_t)p * dd + e];
-    G[e] = s;
-}
-
-int gram_splits(int64_t n, int d) {
-    const int64_t tiles = ceil_div(d, GR_T) * ceil_div(d, GR_T);
-    int64_t s = std::max<int64_t>(1, ceil_div(512, tiles));          // >= 2 rounds of workgroups
-    s = std::min<int64_t>(s, std::max<int64_t>(1, ceil_div(n, 4 * GR_K)));  // >= 4 K steps each
-    return (int)std::min<int64_t>(s, 64);
-}
-
 template <class T, int WR, int WC, int RB, int CB>
 int launch_split(const float* x, int64_t n, int d, const float* rs, const _Float16* bimg, const float* hdr, float* y,
                  hipStream_t st) {
@@ -618,34 +510,4 @@ extern "C" int mivq_opq_rotate_prepared(const float* x, int64_t n, int32_t d, co
         if (rc) return rc;
     }
     return MIVQ_OK;
-}
-
-extern "C" size_t mivq_opq_gram_workspace_bytes(int64_t n, int32_t d) {
-    if (n <= 0 || d <= 0) return 0;
-    return (size_t)gram_splits(n, d) * (size_t)d * d * sizeof(double);
-}
-
-extern "C" int mivq_opq_gram(const float* x, const float* y, int64_t n, int32_t d, void* workspace,
-                             size_t workspace_bytes, double* G, void* stream) {
-    MIVQ_REQUIRE(n >= 0 && d > 0, MIVQ_ERR_INVALID, "opq_gram: bad sizes n=%lld d=%d", (long long)n, d);
-    MIVQ_REQUIRE(G && (n == 0 || (x && y)), MIVQ_ERR_INVALID, "opq_gram: null pointer");
-    hipStream_t st = as_stream(stream);
-    const int64_t dd = (int64_t)d * d;
-    if (n == 0) {
-        hipError_t e = hipMemsetAsync(G, 0, (size_t)dd * sizeof(double), st);
-        return e == hipSuccess ? MIVQ_OK : set_error(MIVQ_ERR_HIP, "opq_gram: %s", hipGetErrorString(e));
-    }
-    const size_t need = mivq_opq_gram_workspace_bytes(n, d);
-    MIVQ_REQUIRE(workspace && workspace_bytes >= need, MIVQ_ERR_WORKSPACE, "opq_gram: workspace %zu < %zu",
-                 workspace_bytes, need);
-    const int splits = gram_splits(n, d);
-    const int ct = (int)ceil_div(d, GR_T);
-    const int64_t rps = ceil_div(n, splits);
-    double* part = static_cast<double*>(workspace);
-    hipLaunchKernelGGL(opq_gram_kernel, dim3((unsigned)(ct * ct), (unsigned)splits), dim3(256), 0, st, x, y, n, d, rps,
-                       ct, part);
-    int rc = check_launch("opq_gram");
-    if (rc) return rc;
-    hipLaunchKernelGGL(opq_gram_reduce_kernel, dim3((unsigned)ceil_div(dd, 256)), dim3(256), 0, st, part, splits, dd, G);
-    return check_launch("opq_gram_reduce");
 }

@@ -3,7 +3,7 @@
 // The quantizer (PCA rotation, a different number of bits per rotated dimension, a Gaussian-
 // optimal level table per dimension scaled by sqrt(var_d)) is, per row and all in fp64 like numpy:
 //   encode: xc = x - mu                                                       [center]
-//           y  = xc . V              (mivq_extrabitq_rotate, the fp64 MFMA GEMM)
+//           y  = xc . V              (mivq_extrabitq_rotate, the fp64 MFMA GEMM of gemm_f64.hip)
 //           idx_d = searchsorted(mid-levels of dimension d, y_d), side left
 //           row = the idx_d as width_d-bit fields, MSB first, at bit pos_d     [quantize]
 //   decode: y_hat_d = levels_d[idx_d]                                          [dequantize]

@@ -530,26 +530,31 @@ def rabitq_search(codes: torch.Tensor, d: int, centroid: Optional[torch.Tensor],
     return dists, ids
 
 
+# ----------------------------------------------------------------- fp64 GEMM
+def gemm_f64(a: torch.Tensor, b: torch.Tensor, transpose: bool) -> torch.Tensor:
+    """a . b (or a . b^T) for (n, d) a and (d, d) b in fp64 on the library's MFMA GEMM
+    (csrc/gemm_f64.hip; the C entry point keeps its first user's name, mivq_extrabitq_rotate)."""
+    _check(a, "a", torch.float64, 2)
+    _check(b, "b", torch.float64, 2)
+    n, d = a.shape
+    if tuple(b.shape) != (d, d):
+        raise ValueError(f"b shape {tuple(b.shape)} != {(d, d)}")
+    out = torch.empty((n, d), dtype=torch.float64, device=a.device)
+    _call("mivq_extrabitq_rotate", _ptr(a), n, d, _ptr(b), 1 if transpose else 0, _ptr(out), _stream())
+    return out
+
+
 # ----------------------------------------------------------------- Extended RaBitQ
+extrabitq_rotate = gemm_f64  # the o . P / o_hat . P^T rotations (extended_rabitq.py:140,196)
+
+
 def extrabitq_code_size(d: int, nbits: int) -> int:
     return (d * nbits + 7) // 8 + 8
 
 
-def extrabitq_rotate(o: torch.Tensor, P: torch.Tensor, transpose: bool) -> torch.Tensor:
-    """o . P (or o . P^T) in fp64 on the library's MFMA GEMM (extended_rabitq.py:140,196)."""
-    _check(o, "o", torch.float64, 2)
-    _check(P, "P", torch.float64, 2)
-    n, d = o.shape
-    if tuple(P.shape) != (d, d):
-        raise ValueError(f"P shape {tuple(P.shape)} != {(d, d)}")
-    out = torch.empty((n, d), dtype=torch.float64, device=o.device)
-    _call("mivq_extrabitq_rotate", _ptr(o), n, d, _ptr(P), 1 if transpose else 0, _ptr(out), _stream())
-    return out
-
-
 def extrabitq_encode(x: torch.Tensor, c: torch.Tensor, P: torch.Tensor, levels: torch.Tensor,
                      nbits: int) -> torch.Tensor:
-    """Codes of ExtendedRaBitQuantizer.compress (the o . P rotation on mivq_extrabitq_rotate)."""
+    """Codes of ExtendedRaBitQuantizer.compress (the o . P rotation on gemm_f64)."""
     if x.dtype not in (torch.float32, torch.float64):
         raise ValueError(f"extrabitq: unsupported dtype {x.dtype}")
     _check(x, "x", x.dtype, 2)
@@ -561,7 +566,7 @@ def extrabitq_encode(x: torch.Tensor, c: torch.Tensor, P: torch.Tensor, levels: 
     nrm = torch.empty((n,), dtype=torch.float64, device=x.device)
     _call("mivq_extrabitq_normalize", _ptr(x), 1 if x.dtype == torch.float64 else 0, n, d, _ptr(c), _ptr(o),
           _ptr(nrm), _stream())
-    s_raw = extrabitq_rotate(o, P, False)
+    s_raw = gemm_f64(o, P, False)
     codes = torch.empty((n, extrabitq_code_size(d, nbits)), dtype=torch.uint8, device=x.device)
     _call("mivq_extrabitq_quantize", _ptr(s_raw), n, d, _ptr(levels), nbits, _ptr(nrm), _ptr(codes), _stream())
     return codes
@@ -576,7 +581,7 @@ def extrabitq_decode(codes: torch.Tensor, c: torch.Tensor, P: torch.Tensor, leve
         raise ValueError(f"codes have {codes.shape[1]} bytes per row, expected {extrabitq_code_size(d, nbits)}")
     o_hat = torch.empty((n, d), dtype=torch.float64, device=codes.device)
     _call("mivq_extrabitq_dequantize", _ptr(codes), n, d, _ptr(levels), nbits, _ptr(o_hat), _stream())
-    y = extrabitq_rotate(o_hat, P, True)
+    y = gemm_f64(o_hat, P, True)
     out = torch.empty((n, d), dtype=torch.float32, device=codes.device)
     _call("mivq_extrabitq_finish", _ptr(y), n, d, _ptr(codes), nbits, _ptr(c), _ptr(out), _stream())
     return out
@@ -718,13 +723,13 @@ def rankaware_finish(z: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
 
 
 def rankaware_encode(x: torch.Tensor, st: RankAwareState) -> torch.Tensor:
-    """Codes of RankAwareQuantizer.compress: center, (x - mu) . V on mivq_extrabitq_rotate, quantize."""
-    return rankaware_quantize(extrabitq_rotate(rankaware_center(x, st.mu), st.V, False), st)
+    """Codes of RankAwareQuantizer.compress: center, (x - mu) . V on gemm_f64, quantize."""
+    return rankaware_quantize(gemm_f64(rankaware_center(x, st.mu), st.V, False), st)
 
 
 def rankaware_decode(codes: torch.Tensor, st: RankAwareState) -> torch.Tensor:
-    """RankAwareQuantizer.decompress: dequantize, y_hat . V^T on mivq_extrabitq_rotate, finish."""
-    return rankaware_finish(extrabitq_rotate(rankaware_dequantize(codes, st), st.V, True), st.mu)
+    """RankAwareQuantizer.decompress: dequantize, y_hat . V^T on gemm_f64, finish."""
+    return rankaware_finish(gemm_f64(rankaware_dequantize(codes, st), st.V, True), st.mu)
 
 
 # ----------------------------------------------------------------- ADC / flat search

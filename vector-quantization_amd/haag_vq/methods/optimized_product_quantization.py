@@ -84,13 +84,13 @@ class OPQHandle:
 
 def _mm(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """a . b for square fp64 device matrices on the library's fp64 MFMA GEMM."""
-    return _native.extrabitq_rotate(a.contiguous(), b.contiguous(), False)
+    return _native.gemm_f64(a.contiguous(), b.contiguous(), False)
 
 
 def polar_factor(G: torch.Tensor, tol: float = 1e-13, max_iter: int = 60, info: dict | None = None) -> torch.Tensor:
     """The orthogonal polar factor Q = U V^T of a square fp64 matrix G = U S V^T (what
     faiss OPQMatrix::train takes from its SVD), by the Newton-Schulz iteration
-    Q <- Q (3 I - Q^T Q) / 2 on the fp64 MFMA GEMM (erq_rotate_kernel) instead of rocsolver's
+    Q <- Q (3 I - Q^T Q) / 2 on the fp64 MFMA GEMM (csrc/gemm_f64.hip) instead of rocsolver's
     SVD.  Start: G divided by an UPPER bound of its largest singular value,
     min(||G||_F, sqrt(||G^T G||_inf)), so every scaled singular value lies in (0, 1] and the
     iteration takes each of them to +1 (a start value above sqrt(3) goes to -1 or diverges, and
