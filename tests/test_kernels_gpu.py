@@ -219,17 +219,7 @@ def test_gemm_f64_generic_and_fast_kernels_agree(dev, d, dp, transpose):
     np.testing.assert_array_equal(padded[:, d:], 0.0)
 
 
-def _prep_offsets(M, dsub, ksub=256):
-    """Byte offsets inside the mivq_pq_prepare buffer (mirror of PqPrepLayout, mivq_common.h)."""
-    al = lambda v: (v + 255) // 256 * 256  # noqa: E731
-    ks = (dsub + 15) // 16
-    L, off = {}, 0
-    for name, size in (("cn", 4 * M * ksub), ("ct", 4 * M * dsub * ksub), ("img", M * 8 * ks * 64 * 16),
-                       ("hinit", 4 * M * ksub), ("bnd", 16 * M), ("spread", 8 * M),
-                       ("pd", M * 256 * 256 * 8 if M <= 64 else 0), ("bnd2", 16 * M)):
-        L[name] = off
-        off = al(off + size)
-    return L
+from _pq_filter_rule import prep_offsets as _prep_offsets  # noqa: E402
 
 
 @pytest.mark.parametrize("d,M", [(1536, 16), (1024, 16), (200, 4)])
