@@ -241,6 +241,38 @@ int mivq_rankaware_dequantize(const uint8_t* codes, int64_t n, int32_t d, const 
 int mivq_rankaware_finish(const double* z, int64_t n, int32_t d, const double* mu, float* out,
                           void* stream);
 
+/* Exact top-k over rank-aware codes in the rotated domain, without decoding them.  V is
+ * orthogonal and x^ = y^ . V^T + mu, so ||q - x^||^2 = ||(q - mu) V - y^||^2 and
+ * <q, x^> = <q V, y^> + <q, mu>: the caller passes the rotated queries qy (nq, d) f32 (L2:
+ * (q - mu) V, IP: q V) and, for IP, adds <q, mu> to the scores it gets back.
+ *   y^_{i,t} = lv32[lv_off[t] + idx_{i,t}], idx_{i,t} the width[t] bits at bit pos[t] of row i,
+ *              read exactly as mivq_rankaware_dequantize reads them (width 0: index 0, the
+ *              table's one entry; bits of no field are ignored; a field outside the row or a
+ *              width outside 0..8 is width 0; no byte pattern indexes outside a table).
+ *              lv32 is lv rounded to f32 (round to nearest), same offsets.
+ *   L2: dist = fmaf chain over t ascending of (qy_t - y^_t)^2, the difference one rounding
+ *   IP: dist = -(fmaf chain over t ascending of qy_t y^_t)
+ * Zero-width dimensions keep their place in the chain.  The k smallest (dist, id) per query in
+ * ascending (dist, id) order, id = id_offset + row, ties to the smaller id, NaN ranked as +inf,
+ * missing slots (+inf, 0xFFFFFFFF): the chains and the order of mivq_flat_search, so dists and
+ * ids are bit-identical to mivq_flat_search(qy, (float)mivq_rankaware_dequantize(codes)).  No
+ * decoded row is written anywhere; the workspace holds top-k lists (few queries) or a block of
+ * keys (nq >= 16 and n >= 4096), never rows.  Rows may start at any byte, and no byte past
+ * codes + n * code_size is read.
+ * nq < 0, n < 0, d <= 0, code_size <= 0, k <= 0, a metric that is neither MIVQ_METRIC_L2 nor
+ * MIVQ_METRIC_INNER_PRODUCT, ids that overflow 32 bits, or a null pointer with nq, n > 0 return
+ * MIVQ_ERR_INVALID before any launch; n == 0 fills dists / ids with the missing-slot values;
+ * k > 256, code_size above 48000 bytes, and (few queries only) d above 16384 are
+ * MIVQ_ERR_UNSUPPORTED.  Any widths are accepted: the level tables (up to 256 d floats) are
+ * staged per slice of dimensions. */
+size_t mivq_rankaware_flat_search_workspace_bytes(int64_t nq, int64_t n, int32_t d,
+                                                  int32_t code_size, int32_t k);
+int mivq_rankaware_flat_search(const float* qy, int64_t nq, const uint8_t* codes, int64_t n,
+                               int32_t d, const float* lv32, const int32_t* lv_off,
+                               const int32_t* pos, const int32_t* width, int32_t code_size,
+                               int32_t metric, int32_t k, int64_t id_offset, void* workspace,
+                               size_t workspace_bytes, float* dists, uint32_t* ids, void* stream);
+
 /* ------------------------------------------------------ ADC search
  * Flat asymmetric-distance search over PQ codes; the GPU counterpart of
  * FlatQuantizedIndex.search_with_scores (methods/search/flat_quantized_index.py:45-76),

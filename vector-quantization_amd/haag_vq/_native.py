@@ -82,6 +82,9 @@ SIGNATURES = {
     "mivq_rankaware_quantize": (_c.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "mivq_rankaware_dequantize": (_c.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "mivq_rankaware_finish": (_c.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
+    "mivq_rankaware_flat_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
+    "mivq_rankaware_flat_search": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64,
+                                              _vp, _sz, _vp, _vp, _vp]),
     "mivq_adc_lut": (_c.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
     "mivq_adc_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
     "mivq_adc_search": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _sz, _vp, _vp, _c.c_uint32,
@@ -590,7 +593,9 @@ def extrabitq_decode(codes: torch.Tensor, c: torch.Tensor, P: torch.Tensor, leve
 # ----------------------------------------------------------------- rank-aware quantizer
 class RankAwareState(NamedTuple):
     """The device side of a fitted RankAwareQuantizer: mu (d,) f64, V (d, d) f64 and the four
-    format tables of include/mivq.h (lv f64, lv_off / pos / width int32)."""
+    format tables of include/mivq.h (lv f64, lv_off / pos / width int32).  ``lv32`` is lv rounded
+    to f32, the table of the code search; rankaware_lv32 derives it where a state was built
+    without it."""
     mu: torch.Tensor
     V: torch.Tensor
     lv: torch.Tensor
@@ -598,6 +603,7 @@ class RankAwareState(NamedTuple):
     pos: torch.Tensor
     width: torch.Tensor
     code_size: int
+    lv32: Optional[torch.Tensor] = None
 
 
 def rankaware_tables(cb, bits, pos, code_size: int):
@@ -647,7 +653,8 @@ def rankaware_state(mu, V, cb, bits, pos, code_size: int, device: Optional[torch
     if mu.shape != (d,) or V.shape != (d, d):
         raise ValueError(f"rankaware: mu {mu.shape} / V {V.shape} do not match d={d}")
     dev = device if device is not None else require_device()
-    return RankAwareState(*(torch.from_numpy(a).to(dev) for a in (mu, V, lv, lv_off, pos, width)), int(code_size))
+    st = RankAwareState(*(torch.from_numpy(a).to(dev) for a in (mu, V, lv, lv_off, pos, width)), int(code_size))
+    return st._replace(lv32=st.lv.to(torch.float32))
 
 
 def _rankaware_check(st: RankAwareState) -> int:
@@ -730,6 +737,54 @@ def rankaware_encode(x: torch.Tensor, st: RankAwareState) -> torch.Tensor:
 def rankaware_decode(codes: torch.Tensor, st: RankAwareState) -> torch.Tensor:
     """RankAwareQuantizer.decompress: dequantize, y_hat . V^T on gemm_f64, finish."""
     return rankaware_finish(gemm_f64(rankaware_dequantize(codes, st), st.V, True), st.mu)
+
+
+_LV32_CACHE: dict = {}  # states built without lv32: (lv storage, version) -> (lv, its f32 rounding)
+
+
+def rankaware_lv32(st: RankAwareState) -> torch.Tensor:
+    """The f32 level table of the code search: st.lv rounded to nearest, derived once per state."""
+    if st.lv32 is not None:
+        return st.lv32
+    key = (st.lv.data_ptr(), st.lv.numel(), st.lv._version, st.lv.device)
+    hit = _LV32_CACHE.get(key)
+    if hit is None or hit[0] is not st.lv:
+        if len(_LV32_CACHE) >= 16:
+            _LV32_CACHE.clear()
+        hit = _LV32_CACHE[key] = (st.lv, st.lv.to(torch.float32))
+    return hit[1]
+
+
+def rankaware_flat_search(qy: torch.Tensor, codes: torch.Tensor, st: RankAwareState, k: int, metric: int = METRIC_L2,
+                          id_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact top-k of the rotated queries qy over rank-aware codes without decoding them
+    (mivq_rankaware_flat_search): the same (dists f32 (nq, k), ids int32 (nq, k) holding uint32
+    ids) as flat_search(qy, rankaware_dequantize(codes, st).float())."""
+    d = _rankaware_check(st)
+    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.uint8 or codes.dim() != 2:
+        raise ValueError(f"rankaware_flat_search: codes must be a 2-D uint8 tensor, got "
+                         f"{tuple(getattr(codes, 'shape', ()))} {getattr(codes, 'dtype', type(codes))}")
+    if codes.shape[1] != st.code_size:
+        raise ValueError(f"codes have {codes.shape[1]} bytes per row, expected {st.code_size}")
+    _check(codes, "codes", torch.uint8, 2)
+    if not codes.is_contiguous():
+        raise ValueError("codes must be a contiguous device tensor")
+    _check(qy, "qy", torch.float32, 2)
+    if not qy.is_contiguous():
+        raise ValueError("qy must be contiguous")
+    if qy.shape[1] != d:
+        raise ValueError(f"codes have d={d}, queries d={qy.shape[1]}")
+    lv32 = rankaware_lv32(st)
+    _check(lv32, "lv32", torch.float32, 1)
+    if lv32.numel() != st.lv.numel():
+        raise ValueError(f"rankaware: lv32 has {lv32.numel()} entries, lv {st.lv.numel()}")
+    nq, n = qy.shape[0], codes.shape[0]
+    dists = torch.empty((nq, k), dtype=torch.float32, device=qy.device)
+    ids = torch.empty((nq, k), dtype=torch.int32, device=qy.device)
+    ws = workspace(load_library().mivq_rankaware_flat_search_workspace_bytes(nq, n, d, st.code_size, k), qy.device)
+    _call("mivq_rankaware_flat_search", _ptr(qy), nq, _ptr(codes), n, d, _ptr(lv32), _ptr(st.lv_off), _ptr(st.pos),
+          _ptr(st.width), st.code_size, metric, k, id_offset, _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids), _stream())
+    return dists, ids
 
 
 # ----------------------------------------------------------------- ADC / flat search

@@ -16,6 +16,8 @@ Where the work runs:
   on ``(seed + b, 2 ** b)`` and are cached per process.
 * ``compress`` / ``decompress``: ``mivq_rankaware_center`` -> ``mivq_extrabitq_rotate`` (the
   fp64 MFMA GEMM) -> ``mivq_rankaware_quantize`` and the mirror image, fp64 throughout.
+* ``search_codes``: the queries are rotated (``rotate_queries``, fp64, rounded once) and the
+  packed codes are scanned as they are (``mivq_rankaware_flat_search``); no row is decoded.
 
 Parity: the GEMM's summation order differs from numpy's, so an index can differ from the
 reference's only by one and only where the rotated value lies within rounding distance of the
@@ -231,6 +233,47 @@ class RankAwareQuantizer(BaseQuantizer):
         for s, e in _arrays.row_chunks(codes.shape[0], self.D * 24, self._stage_bytes):
             out[s:e] = _arrays.to_host(_native.rankaware_decode(_arrays.to_device(codes[s:e], torch.uint8), st))
         return out
+
+    # --------------------------------------------------------------- search
+    def _queries(self, Q) -> torch.Tensor:
+        if self.V is None:
+            raise RuntimeError("Quantizer must be fit before a search.")
+        if not _arrays.is_tensor(Q):
+            Q = np.ascontiguousarray(Q)
+        if len(Q.shape) != 2 or Q.shape[1] != self.D:
+            raise ValueError(f"queries must be (nq, {self.D}), got shape {tuple(Q.shape)}")
+        dt = torch.float64 if str(Q.dtype).endswith("float64") else torch.float32
+        return _arrays.to_device(Q, dt).contiguous()
+
+    def rotate_queries(self, Q, metric: str = "l2") -> torch.Tensor:
+        """The queries in the rotated domain, (nq, D) f32 on the device: ``(Q - mu) V`` for L2 and
+        ``Q V`` for IP, computed in fp64 and rounded once."""
+        if metric not in ("l2", "ip"):
+            raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
+        Qd = self._queries(Q)
+        st = self._state()
+        mu = st.mu if metric == "l2" else torch.zeros_like(st.mu)
+        return _native.gemm_f64(_native.rankaware_center(Qd, mu), st.V, False).to(torch.float32)
+
+    def search_codes(self, codes, Q, k: int, metric: str = "l2", id_offset: int = 0):
+        """Top-k of Q over ``codes`` without decoding them (``mivq_rankaware_flat_search``, k <= 256).
+
+        V is orthogonal and x_hat = y_hat V^T + mu, so ||q - x_hat||^2 = ||(q - mu) V - y_hat||^2
+        and <q, x_hat> = <q V, y_hat> + <q, mu>: only the queries are rotated, the codes are
+        scanned as packed fields against the per-dimension level tables.  Returns device tensors
+        (dists f32 (nq, k), ids int32 (nq, k) holding uint32 ids): squared L2 distances ascending,
+        or inner products descending (the kernel's key negated plus f32(<q, mu>), one f32 add per
+        query)."""
+        Qy = self.rotate_queries(Q, metric)
+        st = self._state()
+        cd = codes if _arrays.is_tensor(codes) else torch.from_numpy(np.ascontiguousarray(codes, dtype=np.uint8))
+        cd = _arrays.to_device(cd, torch.uint8).contiguous()
+        mt = _native.METRIC_L2 if metric == "l2" else _native.METRIC_INNER_PRODUCT
+        d, i = _native.rankaware_flat_search(Qy, cd, st, int(k), mt, id_offset=int(id_offset))
+        if metric == "ip":
+            qmu = (self._queries(Q).to(torch.float64) @ st.mu).to(torch.float32)
+            d = -d + qmu[:, None]
+        return d, i
 
     def get_compression_ratio(self, X) -> float:
         return float(int(X.shape[1]) * 4 / self.code_size)

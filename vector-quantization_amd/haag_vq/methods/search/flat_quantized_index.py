@@ -17,8 +17,12 @@ bytes, ``save`` / ``load`` round-trip the index.  The reference decodes every co
 * LVQ codes likewise (``mivq_lvq_flat_search``: the MSB-first bit stream and the per-row
   ``lo`` / ``delta`` read in the scan, the ids and distances of ``mivq_lvq_decode`` +
   ``mivq_flat_search`` bit for bit).
-* other quantizers (f64-fitted SQ, Extended RaBitQ, ...) are decoded on the device and searched
-  exactly (``mivq_flat_search``).
+* other quantizers (f64-fitted SQ, Extended RaBitQ, rank-aware, ...) are decoded on the device
+  and searched exactly (``mivq_flat_search``).
+
+``RankAwareFlatIndex`` searches rank-aware codes without decoding them: the queries are rotated
+onto the PCA axes and the packed fields are scanned against the per-dimension level tables
+(``mivq_rankaware_flat_search``).
 
 Ties are broken by the smaller id.  Saved indices are ``.npz`` archives of plain arrays
 (loaded with ``allow_pickle=False``).
@@ -271,3 +275,38 @@ class FlatADCIndex(FlatQuantizedIndex):
         if not isinstance(quantizer, (ProductQuantizer, OptimizedProductQuantizer)):
             raise ValueError("FlatADCIndex needs a ProductQuantizer or OptimizedProductQuantizer")
         super().__init__(quantizer)
+
+
+class RankAwareFlatIndex(FlatQuantizedIndex):
+    """FlatQuantizedIndex over RankAwareQuantizer codes, searched in the rotated domain.
+
+    ``FlatQuantizedIndex`` decodes the whole database on every call (dequantize, an N x D x D
+    fp64 product, two N x D fp64 intermediates).  Here only the queries are rotated
+    (``RankAwareQuantizer.search_codes``): ||q - x_hat||^2 = ||(q - mu) V - y_hat||^2 for the
+    orthogonal V.  Distances differ from the decode path's by fp32 rounding (the sum runs over the
+    rotated coordinates), so near-ties may rank differently; k > 256 takes the inherited path.
+    Index files are those of FlatQuantizedIndex: either class loads the other's."""
+
+    def __init__(self, quantizer: BaseQuantizer) -> None:
+        if not isinstance(quantizer, RankAwareQuantizer):
+            raise ValueError("RankAwareFlatIndex needs a RankAwareQuantizer")
+        super().__init__(quantizer)
+
+    def search_with_scores(self, Q, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        if min(int(k), self._N) > MAX_KERNEL_K:
+            return super().search_with_scores(Q, k)
+        Q = np.ascontiguousarray(Q, dtype=np.float32) if not _arrays.is_tensor(Q) else Q
+        nq = Q.shape[0]
+        k = min(int(k), self._N)
+        if k <= 0:
+            return np.empty((nq, 0), dtype=np.uint32), np.empty((nq, 0), dtype=np.float32)
+        d, i = self._quantizer.search_codes(self._codes, Q, k, self._metric)
+        return ids_to_numpy(i), _arrays.to_host(d)
+
+    def load(self, path: str | Path) -> None:
+        got = FlatQuantizedIndex(self._quantizer)
+        got.load(path)
+        if not isinstance(got._quantizer, RankAwareQuantizer):
+            raise ValueError(f"load(): {path} holds a {type(got._quantizer).__name__}, not a RankAwareQuantizer")
+        self._quantizer, self._codes, self._metric = got._quantizer, got._codes, got._metric
+        self._N, self._D = got._N, got._D
