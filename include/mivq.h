@@ -205,6 +205,25 @@ int mivq_extrabitq_finish(const double* y, int64_t n, int32_t d, const uint8_t* 
 /* s = o . P (transpose 0) or o . P^T (transpose 1); o, s: (n, d) f64 row-major, P: (d, d). */
 int mivq_extrabitq_rotate(const double* o, int64_t n, int32_t d, const double* P, int32_t transpose,
                           double* s, void* stream);
+/* Exact top-k over Extended RaBitQ codes, undecoded, in the rotated domain.  P is orthogonal and
+ * x_hat = (o_hat . P^T) nrm + c, so ||q - x_hat||^2 = ||(q - c) P - y_hat||^2 and
+ * <q, x_hat> = <q P, y_hat> + <q, c> with y_hat = o_hat nrm: the caller rotates the queries
+ * (qy = (q - c) P for L2, q P for inner product; (nq, d) f32) and the rows are scanned as codes.
+ *   o_hat_t = dmul(ddiv(levels[idx_t], sqrt((double)d)), (double)t)   the bits dequantize writes
+ *   y_hat_t = (float)dmul(o_hat_t, (double)nrm)                       one more fp64 product, one rounding
+ *   L2: dist = fmaf chain over t ascending of (qy_t - y_hat_t)^2, the difference rounded once
+ *   IP: dist = -(fmaf chain over t ascending of qy_t * y_hat_t)
+ * idx_t is the B bits at bit t*B of the row, MSB first; nrm and t are the two trailer floats in
+ * that order; bits past d*B in the last code byte are ignored; rows may start at any byte.
+ * The k smallest (dist, id) per query, every convention of mivq_flat_search (ascending, ties to
+ * the smaller id, NaN as +inf, missing slots (+inf, 0xFFFFFFFF), id = id_offset + row): the
+ * result is bit-identical to mivq_flat_search(qy, y_hat).  levels: 2^nbits f64 on the device,
+ * nbits in [1, 8], k <= 256.  The workspace holds top-k lists or a block of keys, never rows. */
+size_t mivq_extrabitq_flat_search_workspace_bytes(int64_t nq, int64_t n, int32_t d, int32_t k);
+int mivq_extrabitq_flat_search(const float* qy, int64_t nq, const uint8_t* codes, int64_t n, int32_t d,
+                               const double* levels, int32_t nbits, int32_t metric, int32_t k,
+                               int64_t id_offset, void* workspace, size_t workspace_bytes,
+                               float* dists, uint32_t* ids, void* stream);
 
 /* ------------------------------------------------------ Rank-aware quantizer (PCA + bits per dimension)
  * The per-row steps of RankAwareQuantizer.compress / decompress (rank_aware_quantization.py),

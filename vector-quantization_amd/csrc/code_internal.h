@@ -11,25 +11,30 @@
 
 namespace mivq {
 
-// kLvq + B - 1 is LVQ with B bits per dimension, B = 1 .. 8; kF32 is the database itself
-enum : int { kSq4 = 0, kSq8 = 1, kSq16 = 2, kRbq = 3, kLvq = 4, kF32 = 12 };
+// kLvq + B - 1 is LVQ with B bits per dimension, B = 1 .. 8; kF32 is the database itself;
+// kErq + B - 1 is Extended RaBitQ with B bits per dimension, in the rotated domain
+enum : int { kSq4 = 0, kSq8 = 1, kSq16 = 2, kRbq = 3, kLvq = 4, kF32 = 12, kErq = 13 };
+
+constexpr int kErqTableBytes = 256 * 8;  // the 2^B level table of a workgroup, at B = 8
 
 // Queries per scan workgroup: the queries and the `params` parameter rows of dp = d rounded up
-// to 4 floats share the LDS, within `lds_kib` at 8, 4 or 2 queries and 160 KiB at one.
+// to 4 floats share the LDS, within `lds_kib` at 8, 4 or 2 queries and 160 KiB at one, less
+// the `table` bytes a format keeps there besides.
 struct ScanPolicy {
     int params;
     int lds_kib;
     bool narrow;  // no wider than the batch (search_layout)
+    int table = 0;
 };
 
 // Queries per scan workgroup under policy P, before narrowing; 0: d does not fit the LDS.
 inline int scan_qb(int d, ScanPolicy P) {
     const int64_t per = (int64_t)((d + 3) & ~3) * 4;
-    const int64_t budget = (int64_t)P.lds_kib * 1024;
+    const int64_t budget = (int64_t)P.lds_kib * 1024 - P.table;
     if (per * (8 + P.params) <= budget) return 8;
     if (per * (4 + P.params) <= budget) return 4;
     if (per * (2 + P.params) <= budget) return 2;
-    if (per * (1 + P.params) <= 160 * 1024) return 1;
+    if (per * (1 + P.params) <= 160 * 1024 - P.table) return 1;
     return 0;
 }
 
@@ -37,27 +42,32 @@ inline int scan_qb(int d, ScanPolicy P) {
 template <int FMT>
 struct Fmt {
     static constexpr bool kIsLvq = FMT >= kLvq && FMT < kLvq + 8;
-    static constexpr int kB = kIsLvq ? FMT - kLvq + 1 : 0;  // LVQ bits per dimension
+    static constexpr bool kIsErq = FMT >= kErq && FMT < kErq + 8;
+    // LVQ and Extended RaBitQ rows are the same stream: ceil(d kB / 8) bytes of MSB-first kB-bit
+    // fields, then a trailer of two f32 (LVQ {lo, delta}, Extended RaBitQ {nrm, t})
+    static constexpr bool kIsStream = kIsLvq || kIsErq;
+    static constexpr int kB = kIsLvq ? FMT - kLvq + 1 : kIsErq ? FMT - kErq + 1 : 0;  // bits per dimension
     static constexpr uint32_t kMask = (1u << kB) - 1u;
-    // dims per 32-bit word of codes (LVQ: per unit of kB words)
+    // dims per 32-bit word of codes (a stream: per unit of kB words)
     static constexpr int kWordDims = FMT == kSq4 ? 8 : FMT == kSq8 ? 4 : FMT == kSq16 ? 2 : FMT == kF32 ? 1 : 32;
-    // words per wide load of the scan (16 B; 8 B for RaBitQ and LVQ, whose rows of d % 64 == 0
+    // words per wide load of the scan (16 B; 8 B for RaBitQ and the streams, whose rows of d % 64 == 0
     // are 8-B aligned: the 8-byte trailer follows a multiple of 8 code bytes)
-    static constexpr int kWideWords = FMT == kRbq || kIsLvq ? 2 : 4;
-    // per-dimension parameter arrays: SQ {den, lo}, RaBitQ {centroid}, LVQ {mu}, f32 none
-    static constexpr int kParams = FMT == kF32 ? 0 : FMT == kRbq || kIsLvq ? 1 : 2;
+    static constexpr int kWideWords = FMT == kRbq || kIsStream ? 2 : 4;
+    // per-dimension parameter arrays: SQ {den, lo}, RaBitQ {centroid}, LVQ {mu}, f32 and
+    // Extended RaBitQ none (its one table of 2^kB levels is shared by all dimensions)
+    static constexpr int kParams = FMT == kF32 || kIsErq ? 0 : FMT == kRbq || kIsLvq ? 1 : 2;
     // The f32 scan keeps the launch policy it had as a kernel of its own: 96 KiB where the code
     // formats take 128, and a query block that is not narrowed to the batch.  The difference is
     // inherited, not measured: nobody has timed either format under the other's policy.
-    static constexpr ScanPolicy kPolicy = {kParams, FMT == kF32 ? 96 : 128, FMT != kF32};
+    static constexpr ScanPolicy kPolicy = {kParams, FMT == kF32 ? 96 : 128, FMT != kF32, kIsErq ? kErqTableBytes : 0};
     static constexpr float kLevels = FMT == kSq4 ? 15.0f : FMT == kSq8 ? 255.0f : 65535.0f;
     static constexpr float kRcpLevels = 1.0f / kLevels;  // RN(1 / L)
 
     __host__ __device__ static int code_bytes(int d) {
-        if (kIsLvq) return (int)(((int64_t)d * kB + 7) / 8);
+        if (kIsStream) return (int)(((int64_t)d * kB + 7) / 8);
         return FMT == kSq4 ? (d + 1) / 2 : FMT == kSq8 ? d : FMT == kSq16 ? 2 * d : FMT == kF32 ? 4 * d : (d + 7) / 8;
     }
-    __host__ __device__ static int row_bytes(int d) { return code_bytes(d) + (FMT == kRbq || kIsLvq ? 8 : 0); }
+    __host__ __device__ static int row_bytes(int d) { return code_bytes(d) + (FMT == kRbq || kIsStream ? 8 : 0); }
     // byte offset of dimension t (a multiple of kWordDims) in a row
     __device__ static int byte_of(int t) {
         return FMT == kSq4 ? t >> 1 : FMT == kSq8 ? t : FMT == kSq16 ? 2 * t : FMT == kF32 ? 4 * t : t >> 3;
@@ -66,7 +76,7 @@ struct Fmt {
     // level (SQ) / sign bit (RaBitQ) / float bits (f32) of dimension u of the little-endian words w[]
     template <int NW>
     __device__ __forceinline__ static uint32_t level(const uint32_t (&w)[NW], int u) {
-        if (kIsLvq) {  // w[]: the unit's words byte-swapped, field u at bits [u kB, (u + 1) kB) from the top
+        if (kIsStream) {  // w[]: the unit's words byte-swapped, field u at bits [u kB, (u + 1) kB) from the top
             const int o = u * kB, wi = o >> 5, end = (o & 31) + kB;
             if (end <= 32) return (w[wi] >> (32 - end)) & kMask;
             return ((w[wi] << (end - 32)) | (w[wi + 1 < NW ? wi + 1 : wi] >> (64 - end))) & kMask;
@@ -82,7 +92,7 @@ struct Fmt {
     }
     // the same for dimension t of row `cr`, one code element at a time
     __device__ __forceinline__ static uint32_t level_at(const uint8_t* cr, int t) {
-        if (kIsLvq) {  // the field lies in two bytes at most (the byte after the last is the trailer's)
+        if (kIsStream) {  // the field lies in two bytes at most (the byte after the last is the trailer's)
             const int o = t * kB, fb = o >> 3;
             const uint32_t v = (uint32_t)cr[fb] << 8 | cr[fb + 1];
             return (v >> (16 - (o & 7) - kB)) & kMask;
@@ -101,8 +111,19 @@ struct Fmt {
     // RaBitQ: a = c_t (0 without a centroid), p.x the row's fmul(fmul(fmul(0.5, mult), 2), 1/sqrt(d)).
     // LVQ: a = mu_t, p = the row's {lo, delta}: fadd(fadd(lo, fmul(idx, delta)), mu_t).
     // f32: the word is x_t.
-    __device__ __forceinline__ static float dequant(uint32_t lv, float a, float b, float2 p) {
+    // Extended RaBitQ: tab[l] = ddiv(levels[l], sqrt(d)), p = the row's {nrm, t}:
+    // (float)dmul(dmul(tab[idx], t), nrm), the level erq_dequantize_kernel writes times nrm.
+    __device__ __forceinline__ static float dequant(uint32_t lv, float a, float b, float2 p,
+                                                    const double* tab = nullptr) {
         if (FMT == kF32) return __uint_as_float(lv);
+        if (kIsErq) {
+            // The empty asm keeps the first products of a group of four in program order.  Left
+            // free, the scheduler holds all four f64 pairs at once, and the scan at 4 list
+            // registers and 8 queries (128 VGPRs allowed) spilled 8 / 16 bytes at B = 3 / 7.
+            double v = __dmul_rn(tab[lv], (double)p.y);
+            asm volatile("" : "+v"(v));
+            return (float)__dmul_rn(v, (double)p.x);
+        }
         if (kIsLvq) return __fadd_rn(__fadd_rn(p.x, __fmul_rn((float)lv, p.y)), a);
         if (FMT == kRbq) return __fadd_rn(lv ? p.x : -p.x, a);
         const float f = (float)lv;
@@ -112,17 +133,18 @@ struct Fmt {
         return __fadd_rn(__fmul_rn(s, a), b);
     }
     // The row's own parameters from its trailer (read byte-wise: rows are unaligned).  RaBitQ: p
-    // in .x, from mult, the second trailer float; LVQ: {lo, delta}, the two trailer floats.
+    // in .x, from mult, the second trailer float; LVQ: {lo, delta}, Extended RaBitQ: {nrm, t}, the
+    // two trailer floats.
     __device__ __forceinline__ static float2 row_scale(const uint8_t* cr, int d) {
-        if (FMT != kRbq && !kIsLvq) return make_float2(0.0f, 0.0f);
+        if (FMT != kRbq && !kIsStream) return make_float2(0.0f, 0.0f);
         const int nb = code_bytes(d);
         uint32_t u0 = 0, u1 = 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            if (kIsLvq) u0 |= (uint32_t)cr[nb + q] << (8 * q);
+            if (kIsStream) u0 |= (uint32_t)cr[nb + q] << (8 * q);
             u1 |= (uint32_t)cr[nb + 4 + q] << (8 * q);
         }
-        if (kIsLvq) return make_float2(__uint_as_float(u0), __uint_as_float(u1));
+        if (kIsStream) return make_float2(__uint_as_float(u0), __uint_as_float(u1));
         const float inv_d_sqrt = __fdiv_rn(1.0f, sqrtf((float)d));
         return make_float2(__fmul_rn(__fmul_rn(__fmul_rn(0.5f, __uint_as_float(u1)), 2.0f), inv_d_sqrt), 0.0f);
     }
@@ -131,29 +153,31 @@ struct Fmt {
 // ---------------------------------------------------------------- one row against QB queries
 // Where a workgroup's LDS rows are: [QB][dp] queries at qv, the parameter rows pa (SQ den /
 // RaBitQ centroid / LVQ mu) and pb (SQ lo), and with CENT the row pc that is added to every
-// reconstruction (the list's centroid: x^_t = dequant + pc_t, one more fadd).
+// reconstruction (the list's centroid: x^_t = dequant + pc_t, one more fadd); tab: the
+// Extended RaBitQ level table (Fmt<>::dequant).
 struct ScanRows {
     const float* qv;
     const float* pa;
     const float* pb;
     const float* pc;
     int dp;
+    const double* tab = nullptr;
 };
 
 template <int FMT, bool CENT>
-__device__ __forceinline__ float scan_value(uint32_t lv, float a, float b, float c, float2 p) {
-    const float x = Fmt<FMT>::dequant(lv, a, b, p);
+__device__ __forceinline__ float scan_value(uint32_t lv, float a, float b, float c, float2 p, const double* tab) {
+    const float x = Fmt<FMT>::dequant(lv, a, b, p, tab);
     if constexpr (CENT) return __fadd_rn(x, c);
     return x;
 }
 
 // NW loaded words = NW * kWordDims (a multiple of 4) dimensions from t0 (a multiple of 4) on:
 // four at a time, the parameters and the queries as 16-B LDS reads.  LVQ: the kB byte-swapped
-// words of one unit, 32 dimensions.
+// words of one unit, 32 dimensions; Extended RaBitQ the same.
 template <int FMT, int NW, int QB, bool CENT>
 __device__ __forceinline__ void scan_words(const uint32_t (&w)[NW], int t0, const ScanRows& S, float2 p, bool l2,
                                            float (&dist)[QB]) {
-    constexpr int ND = Fmt<FMT>::kIsLvq ? 32 : NW * Fmt<FMT>::kWordDims;
+    constexpr int ND = Fmt<FMT>::kIsStream ? 32 : NW * Fmt<FMT>::kWordDims;
     static_assert(ND % 4 == 0, "whole groups of four dimensions");
 #pragma unroll
     for (int g = 0; g < ND; g += 4) {
@@ -161,10 +185,10 @@ __device__ __forceinline__ void scan_words(const uint32_t (&w)[NW], int t0, cons
         if constexpr (Fmt<FMT>::kParams >= 1) a4 = *reinterpret_cast<const float4*>(S.pa + t0 + g);
         if constexpr (Fmt<FMT>::kParams == 2) b4 = *reinterpret_cast<const float4*>(S.pb + t0 + g);
         if constexpr (CENT) c4 = *reinterpret_cast<const float4*>(S.pc + t0 + g);
-        const float x0 = scan_value<FMT, CENT>(Fmt<FMT>::level(w, g + 0), a4.x, b4.x, c4.x, p);
-        const float x1 = scan_value<FMT, CENT>(Fmt<FMT>::level(w, g + 1), a4.y, b4.y, c4.y, p);
-        const float x2 = scan_value<FMT, CENT>(Fmt<FMT>::level(w, g + 2), a4.z, b4.z, c4.z, p);
-        const float x3 = scan_value<FMT, CENT>(Fmt<FMT>::level(w, g + 3), a4.w, b4.w, c4.w, p);
+        const float x0 = scan_value<FMT, CENT>(Fmt<FMT>::level(w, g + 0), a4.x, b4.x, c4.x, p, S.tab);
+        const float x1 = scan_value<FMT, CENT>(Fmt<FMT>::level(w, g + 1), a4.y, b4.y, c4.y, p, S.tab);
+        const float x2 = scan_value<FMT, CENT>(Fmt<FMT>::level(w, g + 2), a4.z, b4.z, c4.z, p, S.tab);
+        const float x3 = scan_value<FMT, CENT>(Fmt<FMT>::level(w, g + 3), a4.w, b4.w, c4.w, p, S.tab);
 #pragma unroll
         for (int qq = 0; qq < QB; ++qq) {
             const float4 qf = *reinterpret_cast<const float4*>(S.qv + qq * S.dp + t0 + g);
@@ -186,8 +210,9 @@ __device__ __forceinline__ void scan_words(const uint32_t (&w)[NW], int t0, cons
 // The chains of code row `cr` against the QB queries, into dist[] (zeroed by the caller).  The
 // row is read once: with 16-B (RaBitQ, LVQ: 8-B) loads while whole loads fit and every row start
 // is that aligned (`wide`), then 4-B loads (`narrow`), then single code elements (the tail, and
-// every row of an unaligned database).  An LVQ row is an MSB-first B-bit stream: 32 dimensions
-// are B whole words, read as one unit, byte-swapped, the fields that cross a word funnel-shifted.
+// every row of an unaligned database).  A stream row (LVQ, Extended RaBitQ) is MSB-first B-bit
+// fields: 32 dimensions are B whole words, read as one unit, byte-swapped, the fields that cross
+// a word funnel-shifted.
 template <int FMT, int QB, bool CENT>
 __device__ __forceinline__ void scan_row(const uint8_t* cr, int d, const ScanRows& S, int wide, int narrow, bool l2,
                                          float (&dist)[QB]) {
@@ -196,7 +221,7 @@ __device__ __forceinline__ void scan_row(const uint8_t* cr, int d, const ScanRow
     const int twide = wide ? d / NDW * NDW : 0;  // dimensions covered by whole wide loads
     const float2 p = F::row_scale(cr, d);
     int t = 0;
-    if constexpr (F::kIsLvq) {
+    if constexpr (F::kIsStream) {
         // whole units of 32 dimensions = kB words: 8-B loads (even kB, 8-B aligned rows) or
         // 4-B loads; the rest of the row, and every row of an unaligned database, below
         constexpr int B = F::kB;
@@ -242,7 +267,7 @@ __device__ __forceinline__ void scan_row(const uint8_t* cr, int d, const ScanRow
     }
     for (; t < d; ++t) {
         const float xh = scan_value<FMT, CENT>(F::level_at(cr, t), F::kParams >= 1 ? S.pa[t] : 0.0f,
-                                               F::kParams == 2 ? S.pb[t] : 0.0f, CENT ? S.pc[t] : 0.0f, p);
+                                               F::kParams == 2 ? S.pb[t] : 0.0f, CENT ? S.pc[t] : 0.0f, p, S.tab);
 #pragma unroll
         for (int qq = 0; qq < QB; ++qq) {
             if (l2) {

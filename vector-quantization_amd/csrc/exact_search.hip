@@ -1,5 +1,6 @@
 // exact_search.hip — exact brute-force search on gfx950 over an f32 database
-// (mivq_flat_search, mivq_pairwise_distances) and over SQ-4/8/16, RaBitQ-1 and LVQ-1..8 codes.
+// (mivq_flat_search, mivq_pairwise_distances) and over SQ-4/8/16, RaBitQ-1, LVQ-1..8 and
+// Extended RaBitQ-1..8 codes.
 //
 // One distance chain, two paths, every row format.  A format (Fmt<>, code_internal.h) says how a
 // row's floats are fetched; f32 is the format with no parameters and no dequantisation.  The packed codes
@@ -7,17 +8,21 @@
 // any point.  Every reconstruction x^_t is the float the decode kernels write (sq.hip
 // sq_decode_kernel, rabitq.hip rabitq_decode_kernel, lvq.hip lvq_decode_kernel; one rounding
 // per step, -ffp-contract=off), so a code search's ids and distances are bit-identical to
-// decode + mivq_flat_search.
+// decode + mivq_flat_search.  Extended RaBitQ rows are searched in the rotated domain: the
+// reconstruction is y^_t = (float)(o^_t nrm) with o^_t the f64 erq_dequantize_kernel writes
+// (extrabitq.hip), the queries arrive rotated, and the result is mivq_flat_search(qy, y^).
 //
 //   code_scan_kernel      the streaming scan: grid (nchunks, ceil(nq / QB)); QB queries and the
 //                         per-dimension parameters (SQ: den, lo; RaBitQ: centroid; LVQ: mu;
-//                         f32: none) in LDS, lane = database row, distances as sequential fmaf
-//                         chains over t, WaveTopK lists merged by launch_topk_merge.  A row is
-//                         read with 16-B (RaBitQ, LVQ: 8-B) loads while whole loads fit and the
-//                         rows are that aligned, then 4-B loads, then single code elements (the
-//                         tail, and every row of an unaligned database).  An LVQ row is an
-//                         MSB-first B-bit stream: 32 dimensions are B whole words, read as one
-//                         unit, byte-swapped, the fields that cross a word funnel-shifted.
+//                         f32: none; Extended RaBitQ: none, but its 2^B f64 levels) in LDS,
+//                         lane = database row, distances as sequential fmaf chains over t,
+//                         WaveTopK lists merged by launch_topk_merge.  A row is read with 16-B
+//                         (RaBitQ, LVQ, Extended RaBitQ: 8-B) loads while whole loads fit and
+//                         the rows are that aligned, then 4-B loads, then single code elements
+//                         (the tail, and every row of an unaligned database).  An LVQ or
+//                         Extended RaBitQ row is an MSB-first B-bit stream: 32 dimensions are B
+//                         whole words, read as one unit, byte-swapped, the fields that cross a
+//                         word funnel-shifted.
 //   pairwise_kernel       exact (row, column) distances of two f32 matrices: pairwise_tile
 //                         (pairwise_tile.h, shared with rankaware_search.hip;
 //                         128 x 64 per 256-thread workgroup, 8 x 4 scalar chains per thread,
@@ -26,7 +31,8 @@
 //                         quantizer's exhaustive search, the k-means assignment) and, as
 //                         launch_tiled_topk's TileFn, the tiled path of mivq_flat_search.
 //   code_pairwise_kernel  the same tile as the TileFn of the code searches: the database side of
-//                         a slice is fetched as codes and dequantised before it is stashed.
+//                         a slice is fetched as codes and dequantised before it is stashed
+//                         (Extended RaBitQ: against the workgroup's level table in LDS).
 //
 // The choice between the two paths is flat_use_tiled(nq, n); both produce the same chains.
 #include "adc_internal.h"
@@ -40,8 +46,19 @@ bool flat_use_tiled(int64_t nq, int64_t n) { return nq >= 16 && n >= 4096; }
 
 namespace {
 
+// The level table of an Extended RaBitQ workgroup: tab[l] = ddiv(levels[l], sqrt(d)), the
+// quotient erq_dequantize_kernel forms per element.  The f64 levels arrive in the place of the
+// per-dimension parameters the format does not have (`ga`).
+template <int B>
+__device__ __forceinline__ void erq_stage_table(const float* ga, int d, double* tab, int tid, int nthreads) {
+    const double* levels = reinterpret_cast<const double*>(ga);
+    const double rd = sqrt((double)d);
+    for (int l = tid; l < (1 << B); l += nthreads) tab[l] = __ddiv_rn(levels[l], rd);
+}
+
 // grid (nchunks, ceil(nq / QB)), block 1024.  LDS: [QB][dp] queries, then kParams x [dp]
-// parameters, dp = d rounded up to 4 (16-B aligned rows; the padding is never read).
+// parameters (Extended RaBitQ: the 2^B f64 levels), dp = d rounded up to 4 (16-B aligned rows;
+// the padding is never read).
 // `wide` / `narrow`: every row start is aligned for the wide (16 / 8 B) / the 4-B loads.
 template <int FMT, int R, int QB>
 __global__ __launch_bounds__(kScanWaves * 64) void code_scan_kernel(
@@ -65,6 +82,7 @@ __global__ __launch_bounds__(kScanWaves * 64) void code_scan_kernel(
             if (F::kParams == 2) pb[t] = gb[t];
         }
     }
+    if constexpr (F::kIsErq) erq_stage_table<F::kB>(ga, d, reinterpret_cast<double*>(pa), tid, kScanWaves * 64);
     __syncthreads();
     WaveTopK<R> top[QB];
     float thr_d[QB];
@@ -79,7 +97,7 @@ __global__ __launch_bounds__(kScanWaves * 64) void code_scan_kernel(
     const int64_t rbeg = (int64_t)blockIdx.x * chunk_rows;
     const int64_t rend = min(n, rbeg + chunk_rows);
     const int64_t stride = F::row_bytes(d);
-    const ScanRows rows{qv, pa, pb, nullptr, dp};
+    const ScanRows rows{qv, pa, pb, nullptr, dp, F::kIsErq ? reinterpret_cast<const double*>(pa) : nullptr};
     for (int64_t base = rbeg + (int64_t)wv * 64; base < rend; base += kScanWaves * 64) {
         const int64_t row = base + lane;
         const bool valid = row < rend;
@@ -108,7 +126,7 @@ hipError_t launch_scan(const float* q, int64_t nq, const uint8_t* codes, int64_t
                        const float* gb, int metric, int k, int64_t id_offset, int64_t nch, float* pd, uint32_t* pi,
                        hipStream_t st) {
     using F = Fmt<FMT>;
-    const size_t smem = (size_t)(QB + F::kParams) * ((d + 3) & ~3) * sizeof(float);
+    const size_t smem = (size_t)(QB + F::kParams) * ((d + 3) & ~3) * sizeof(float) + (F::kIsErq ? sizeof(double) << F::kB : 0);
     auto kern = code_scan_kernel<FMT, R, QB>;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return e;
@@ -179,11 +197,18 @@ __global__ __launch_bounds__(256, 2) void code_pairwise_kernel(const float* __re
     const bool yin = gc < m;
     const uint8_t* cr = codes + (yin ? gc : 0) * (int64_t)F::row_bytes(d);
     const float2 p = yin ? F::row_scale(cr, d) : make_float2(0.0f, 0.0f);
+    const double* tab = nullptr;
+    if constexpr (F::kIsErq) {
+        __shared__ double levels_lds[1 << F::kB];
+        erq_stage_table<F::kB>(ga, d, levels_lds, threadIdx.x, 256);
+        __syncthreads();
+        tab = levels_lds;
+    }
     pairwise_tile<IP, 8>(x, n, m, d, xvec, out, [&](int t) __attribute__((always_inline)) {
         f32x4 py = {0.f, 0.f, 0.f, 0.f};
         if (yin && t < d) {
             uint32_t lv[4] = {0u, 0u, 0u, 0u};
-            if (F::kIsLvq) {
+            if (F::kIsStream) {
                 // t % 4 == 0: the four fields are 4 kB bits from a byte or half-byte boundary on,
                 // five bytes at most (those past the code bytes are the trailer's)
                 const int o = t * F::kB, fb = o >> 3;
@@ -219,9 +244,9 @@ __global__ __launch_bounds__(256, 2) void code_pairwise_kernel(const float* __re
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (t + j < d) {
-                    const float a = ga ? ga[t + j] : 0.0f;
+                    const float a = F::kParams >= 1 && ga ? ga[t + j] : 0.0f;
                     const float b = F::kParams == 2 ? gb[t + j] : 0.0f;
-                    py[j] = F::dequant(lv[j], a, b, p);
+                    py[j] = F::dequant(lv[j], a, b, p, tab);
                 }
             }
         }
@@ -453,4 +478,40 @@ extern "C" int mivq_lvq_flat_search(const float* q, int64_t nq, const uint8_t* c
         default: return MIVQ_ERR_INVALID;
     }
 #undef MIVQ_LVQ_SEARCH
+}
+
+extern "C" size_t mivq_extrabitq_flat_search_workspace_bytes(int64_t nq, int64_t n, int32_t d, int32_t k) {
+    return search_workspace_bytes(nq, n, d, k, Fmt<kErq>::kPolicy);
+}
+
+// qy: the queries in the rotated domain ((q - c) P for L2, q P for inner product).  The f64
+// levels travel in the parameter slot of the shared kernels (erq_stage_table).
+extern "C" int mivq_extrabitq_flat_search(const float* qy, int64_t nq, const uint8_t* codes, int64_t n, int32_t d,
+                                          const double* levels, int32_t nbits, int32_t metric, int32_t k,
+                                          int64_t id_offset, void* workspace, size_t workspace_bytes, float* dists,
+                                          uint32_t* ids, void* stream) {
+    MIVQ_REQUIRE(nq >= 0 && n >= 0 && d > 0 && d <= (1 << 27) && k > 0, MIVQ_ERR_INVALID, "extrabitq_flat_search: bad sizes");
+    MIVQ_REQUIRE(nbits >= 1 && nbits <= 8, MIVQ_ERR_INVALID, "num_bits must be in [1, 8], got %d", nbits);
+    hipStream_t st = as_stream(stream);
+    bool done = false;
+    const int rc = search_prologue("extrabitq_flat_search", nq, n, d, Fmt<kErq>::kPolicy, metric, k, id_offset, dists, ids, st, &done);
+    if (rc != MIVQ_OK || done) return rc;
+    MIVQ_REQUIRE(qy && codes && levels, MIVQ_ERR_INVALID, "extrabitq_flat_search: null pointer");
+    const float* lv = reinterpret_cast<const float*>(levels);
+#define MIVQ_ERQ_SEARCH(B)                                                                                             \
+    case B:                                                                                                            \
+        return exact_flat_search<kErq + B - 1>("extrabitq_flat_search", qy, nq, codes, n, d, lv, nullptr, metric, k,   \
+                                              id_offset, workspace, workspace_bytes, dists, ids, st)
+    switch (nbits) {
+        MIVQ_ERQ_SEARCH(1);
+        MIVQ_ERQ_SEARCH(2);
+        MIVQ_ERQ_SEARCH(3);
+        MIVQ_ERQ_SEARCH(4);
+        MIVQ_ERQ_SEARCH(5);
+        MIVQ_ERQ_SEARCH(6);
+        MIVQ_ERQ_SEARCH(7);
+        MIVQ_ERQ_SEARCH(8);
+        default: return MIVQ_ERR_INVALID;
+    }
+#undef MIVQ_ERQ_SEARCH
 }

@@ -99,6 +99,9 @@ SIGNATURES = {
     "mivq_lvq_flat_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "mivq_lvq_flat_search": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i64, _vp, _sz, _vp, _vp,
                                         _vp]),
+    "mivq_extrabitq_flat_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "mivq_extrabitq_flat_search": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i64, _vp, _sz, _vp,
+                                              _vp, _vp]),
     "mivq_topk_merge": (_c.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "mivq_pairwise_distances": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp]),
     "mivq_topk_rows": (_c.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp]),
@@ -575,19 +578,59 @@ def extrabitq_encode(x: torch.Tensor, c: torch.Tensor, P: torch.Tensor, levels: 
     return codes
 
 
+def _extrabitq_code_check(codes: torch.Tensor, d: int, nbits: int, what: str) -> None:
+    if nbits not in range(1, 9):
+        raise ValueError(f"num_bits must be in [1, 8], got {nbits}")
+    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.uint8 or codes.dim() != 2:
+        raise ValueError(f"{what}: codes must be a 2-D uint8 tensor, got "
+                         f"{tuple(getattr(codes, 'shape', ()))} {getattr(codes, 'dtype', type(codes))}")
+    if codes.shape[1] != extrabitq_code_size(d, nbits):
+        raise ValueError(f"codes have {codes.shape[1]} bytes per row, expected {extrabitq_code_size(d, nbits)}")
+    _check(codes, "codes", torch.uint8, 2)
+
+
+def extrabitq_dequantize(codes: torch.Tensor, levels: torch.Tensor, nbits: int, d: int) -> torch.Tensor:
+    """The unit-sphere levels (n, d) f64 the code rows name, times each row's t
+    (mivq_extrabitq_dequantize): o_hat of decode, before the P^T rotation."""
+    _extrabitq_code_check(codes, d, nbits, "extrabitq_dequantize")
+    _check(levels, "levels", torch.float64, 1)
+    if levels.numel() != 1 << nbits:
+        raise ValueError(f"extrabitq: levels has {levels.numel()} entries, expected {1 << nbits}")
+    n = codes.shape[0]
+    o_hat = torch.empty((n, d), dtype=torch.float64, device=codes.device)
+    _call("mivq_extrabitq_dequantize", _ptr(codes), n, d, _ptr(levels), nbits, _ptr(o_hat), _stream())
+    return o_hat
+
+
 def extrabitq_decode(codes: torch.Tensor, c: torch.Tensor, P: torch.Tensor, levels: torch.Tensor,
                      nbits: int) -> torch.Tensor:
     _check(codes, "codes", torch.uint8, 2)
     n = codes.shape[0]
     d = P.shape[0]
-    if codes.shape[1] != extrabitq_code_size(d, nbits):
-        raise ValueError(f"codes have {codes.shape[1]} bytes per row, expected {extrabitq_code_size(d, nbits)}")
-    o_hat = torch.empty((n, d), dtype=torch.float64, device=codes.device)
-    _call("mivq_extrabitq_dequantize", _ptr(codes), n, d, _ptr(levels), nbits, _ptr(o_hat), _stream())
-    y = gemm_f64(o_hat, P, True)
+    y = gemm_f64(extrabitq_dequantize(codes, levels, nbits, d), P, True)
     out = torch.empty((n, d), dtype=torch.float32, device=codes.device)
     _call("mivq_extrabitq_finish", _ptr(y), n, d, _ptr(codes), nbits, _ptr(c), _ptr(out), _stream())
     return out
+
+
+def extrabitq_flat_search(qy: torch.Tensor, codes: torch.Tensor, levels: torch.Tensor, nbits: int, k: int,
+                          metric: int = METRIC_L2, id_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact top-k of the rotated queries qy over Extended RaBitQ codes without decoding them
+    (mivq_extrabitq_flat_search): the same (dists f32 (nq, k), ids int32 (nq, k) holding uint32
+    ids) as flat_search(qy, y_hat) with y_hat = (float)(extrabitq_dequantize(codes) * nrm)."""
+    _check(qy, "qy", torch.float32, 2)
+    d = qy.shape[1]
+    _extrabitq_code_check(codes, d, nbits, "extrabitq_flat_search")
+    _check(levels, "levels", torch.float64, 1)
+    if levels.numel() != 1 << nbits:
+        raise ValueError(f"extrabitq: levels has {levels.numel()} entries, expected {1 << nbits}")
+    nq, n = qy.shape[0], codes.shape[0]
+    dists = torch.empty((nq, k), dtype=torch.float32, device=qy.device)
+    ids = torch.empty((nq, k), dtype=torch.int32, device=qy.device)
+    ws = workspace(load_library().mivq_extrabitq_flat_search_workspace_bytes(nq, n, d, k), qy.device)
+    _call("mivq_extrabitq_flat_search", _ptr(qy), nq, _ptr(codes), n, d, _ptr(levels), nbits, metric, k, id_offset,
+          _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids), _stream())
+    return dists, ids
 
 
 # ----------------------------------------------------------------- rank-aware quantizer

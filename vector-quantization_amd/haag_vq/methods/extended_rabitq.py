@@ -119,5 +119,45 @@ class ExtendedRaBitQuantizer(BaseQuantizer):
                                                                 c, P, lv, self.num_bits))
         return out
 
+    def _queries(self, Q) -> torch.Tensor:
+        if self.P is None:
+            raise RuntimeError("Quantizer must be fit before a search.")
+        if not _arrays.is_tensor(Q):
+            Q = np.ascontiguousarray(Q)
+        if len(Q.shape) != 2 or Q.shape[1] != self.D:
+            raise ValueError(f"queries must be (nq, {self.D}), got shape {tuple(Q.shape)}")
+        dt = torch.float64 if str(Q.dtype).endswith("float64") else torch.float32
+        return _arrays.to_device(Q, dt).contiguous()
+
+    def rotate_queries(self, Q, metric: str = "l2") -> torch.Tensor:
+        """The queries in the rotated domain, (nq, D) f32 on the device: ``(Q - c) P`` for L2 and
+        ``Q P`` for IP, computed in fp64 and rounded once."""
+        if metric not in ("l2", "ip"):
+            raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
+        Qd = self._queries(Q)
+        c, P, _ = self._state()
+        return _native.gemm_f64(_native.rankaware_center(Qd, c if metric == "l2" else torch.zeros_like(c)), P,
+                                False).to(torch.float32)
+
+    def search_codes(self, codes, Q, k: int, metric: str = "l2", id_offset: int = 0):
+        """Top-k of Q over ``codes`` without decoding them (``mivq_extrabitq_flat_search``, k <= 256).
+
+        P is orthogonal and x_hat = (o_hat P^T) nrm + c, so ||q - x_hat||^2 = ||(q - c) P - y_hat||^2
+        and <q, x_hat> = <q P, y_hat> + <q, c> with y_hat = o_hat nrm: only the queries are rotated,
+        the codes are scanned as bit fields against the shared level table.  Returns device tensors
+        (dists f32 (nq, k), ids int32 (nq, k) holding uint32 ids): squared L2 distances ascending,
+        or inner products descending (the kernel's key negated plus f32(<q, c>), one f32 add per
+        query)."""
+        Qy = self.rotate_queries(Q, metric)
+        c, _, lv = self._state()
+        cd = codes if _arrays.is_tensor(codes) else torch.from_numpy(np.ascontiguousarray(codes, dtype=np.uint8))
+        cd = _arrays.to_device(cd, torch.uint8).contiguous()
+        mt = _native.METRIC_L2 if metric == "l2" else _native.METRIC_INNER_PRODUCT
+        d, i = _native.extrabitq_flat_search(Qy, cd, lv, self.num_bits, int(k), mt, id_offset=int(id_offset))
+        if metric == "ip":
+            qc = (self._queries(Q).to(torch.float64) @ c).to(torch.float32)
+            d = -d + qc[:, None]
+        return d, i
+
     def get_compression_ratio(self, X) -> float:
         return float(int(X.shape[1]) * 4 / self.code_size)

@@ -1,8 +1,9 @@
 from .faiss_ivfpq_index import FaissIvfPqIndex
-from .flat_quantized_index import FlatQuantizedIndex, FlatADCIndex, RankAwareFlatIndex, search_codes
+from .flat_quantized_index import (ExtendedRaBitQFlatIndex, FlatQuantizedIndex, FlatADCIndex, RankAwareFlatIndex,
+                                   search_codes)
 from .ivf_quantized_index import IvfQuantizedIndex
 from .rabitq_index import RaBitQIndex
 from .rabitq_ivf_index import RaBitQIVFIndex
 
-__all__ = ["FaissIvfPqIndex", "FlatQuantizedIndex", "FlatADCIndex", "RankAwareFlatIndex", "IvfQuantizedIndex", "RaBitQIndex",
-           "RaBitQIVFIndex", "search_codes"]
+__all__ = ["FaissIvfPqIndex", "FlatQuantizedIndex", "FlatADCIndex", "RankAwareFlatIndex", "ExtendedRaBitQFlatIndex",
+           "IvfQuantizedIndex", "RaBitQIndex", "RaBitQIVFIndex", "search_codes"]

@@ -22,7 +22,9 @@ bytes, ``save`` / ``load`` round-trip the index.  The reference decodes every co
 
 ``RankAwareFlatIndex`` searches rank-aware codes without decoding them: the queries are rotated
 onto the PCA axes and the packed fields are scanned against the per-dimension level tables
-(``mivq_rankaware_flat_search``).
+(``mivq_rankaware_flat_search``).  ``ExtendedRaBitQFlatIndex`` does the same for Extended RaBitQ
+codes: the queries are rotated by P and the bit fields are scanned against the shared level
+table and each row's ``nrm`` / ``t`` (``mivq_extrabitq_flat_search``).
 
 Ties are broken by the smaller id.  Saved indices are ``.npz`` archives of plain arrays
 (loaded with ``allow_pickle=False``).
@@ -39,6 +41,7 @@ import torch
 from ... import _arrays, _native
 from ..base_quantizer import BaseQuantizer
 from ..base_search_index import BaseSearchIndex
+from ..extended_rabitq import ExtendedRaBitQuantizer
 from ..lvq_quantization import LVQQuantizer
 from ..optimized_product_quantization import OptimizedProductQuantizer, OPQHandle
 from ..product_quantization import ProductQuantizer
@@ -148,6 +151,12 @@ def quantizer_state(q: BaseQuantizer) -> dict:
                     var=np.asarray(q.var, dtype=np.float64), bits=np.asarray(q.bits, dtype=np.int64),
                     cb=np.concatenate(q.cb).astype(np.float64), levels=np.concatenate(q._levels).astype(np.float64),
                     Dg=np.asarray(q._Dg, dtype=np.float64))
+    if isinstance(q, ExtendedRaBitQuantizer):
+        if q.P is None:
+            raise ValueError("save(): the ExtendedRaBitQuantizer is not fitted")
+        return dict(qtype=np.array("extrabitq"), num_bits=np.array(q.num_bits), seed=np.array(q.seed), D=np.array(q.D),
+                    c=np.asarray(q.c, dtype=np.float64), P=np.ascontiguousarray(q.P, dtype=np.float64),
+                    levels=np.asarray(q.levels, dtype=np.float64))
     raise ValueError(f"save(): unsupported quantizer {type(q).__name__}")
 
 
@@ -190,6 +199,12 @@ def quantizer_from_state(z) -> BaseQuantizer:
         q._levels = [lv[2 ** b - 1:2 ** (b + 1) - 1] for b in range(q.max_bits + 1)]
         q._Dg = np.array(z["Dg"])
         q._layout()
+    elif qt == "extrabitq":
+        q = ExtendedRaBitQuantizer(num_bits=int(z["num_bits"]), seed=int(z["seed"]))
+        q.D = int(z["D"])
+        q.c, q.P, q.levels = (np.array(z[nm], dtype=np.float64) for nm in ("c", "P", "levels"))
+        if q.c.shape != (q.D,) or q.P.shape != (q.D, q.D) or q.levels.shape != (2 ** q.num_bits,):
+            raise ValueError("load(): inconsistent Extended RaBitQ quantizer state")
     else:
         raise ValueError(f"load(): unknown quantizer type {qt!r}")
     return q
@@ -308,5 +323,47 @@ class RankAwareFlatIndex(FlatQuantizedIndex):
         got.load(path)
         if not isinstance(got._quantizer, RankAwareQuantizer):
             raise ValueError(f"load(): {path} holds a {type(got._quantizer).__name__}, not a RankAwareQuantizer")
+        self._quantizer, self._codes, self._metric = got._quantizer, got._codes, got._metric
+        self._N, self._D = got._N, got._D
+
+
+class ExtendedRaBitQFlatIndex(FlatQuantizedIndex):
+    """FlatQuantizedIndex over ExtendedRaBitQuantizer codes, searched in the rotated domain.
+
+    ``FlatQuantizedIndex`` decodes the whole database on every call (dequantize, an N x D x D
+    fp64 product, an N x D fp32 copy).  Here only the queries are rotated
+    (``ExtendedRaBitQuantizer.search_codes``): ||q - x_hat||^2 = ||(q - c) P - y_hat||^2 for the
+    orthogonal P.  Distances differ from the decode path's by fp32 rounding (the sum runs over the
+    rotated coordinates), so near-ties may rank differently; k > 256 takes the inherited path.
+    Index files are those of FlatQuantizedIndex: either class loads the other's."""
+
+    def __init__(self, quantizer: BaseQuantizer) -> None:
+        if not isinstance(quantizer, ExtendedRaBitQuantizer):
+            raise ValueError("ExtendedRaBitQFlatIndex needs an ExtendedRaBitQuantizer")
+        super().__init__(quantizer)
+
+    def search_with_scores(self, Q, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        if self._codes is None:
+            raise RuntimeError("ExtendedRaBitQFlatIndex must be fit (or loaded) before a search")
+        if min(int(k), self._N) > MAX_KERNEL_K:
+            return super().search_with_scores(Q, k)
+        Q = np.ascontiguousarray(Q, dtype=np.float32) if not _arrays.is_tensor(Q) else Q
+        nq = Q.shape[0]
+        k = min(int(k), self._N)
+        if k <= 0:
+            return np.empty((nq, 0), dtype=np.uint32), np.empty((nq, 0), dtype=np.float32)
+        d, i = self._quantizer.search_codes(self._codes, Q, k, self._metric)
+        return ids_to_numpy(i), _arrays.to_host(d)
+
+    def save(self, path: str | Path) -> None:
+        if self._codes is None:
+            raise RuntimeError("ExtendedRaBitQFlatIndex must be fit (or loaded) before save()")
+        super().save(path)
+
+    def load(self, path: str | Path) -> None:
+        got = FlatQuantizedIndex(self._quantizer)
+        got.load(path)
+        if not isinstance(got._quantizer, ExtendedRaBitQuantizer):
+            raise ValueError(f"load(): {path} holds a {type(got._quantizer).__name__}, not an ExtendedRaBitQuantizer")
         self._quantizer, self._codes, self._metric = got._quantizer, got._codes, got._metric
         self._N, self._D = got._N, got._D
