@@ -20,6 +20,8 @@ import numpy as np
 import pytest
 import torch
 
+from _rabitq_encode_rule import _assert_ties_only
+
 
 def _sha(a) -> str:
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
@@ -76,12 +78,6 @@ def test_sq_wide_oracle_matches_reference(oracle, sqw, mk):
         _check_sq(sqw, tag, c, oracle.sq_decode(c, X.shape[1], lo, den, bits))
 
 
-def _erq_unpack(cb, D, nb):
-    ib = (D * nb + 7) // 8
-    bits = np.unpackbits(cb[:, :ib], axis=1)[:, :D * nb].reshape(len(cb), D, nb)
-    return (bits.astype(np.int64) << np.arange(nb - 1, -1, -1)).sum(-1)
-
-
 def _check_P(erqw, tag, P):
     """The regenerated rotation equals the fixture's to rounding (numpy's QR is bit-identical
     only on the same CPU: the sha is compared where it can be, the samples everywhere; the
@@ -90,21 +86,6 @@ def _check_P(erqw, tag, P):
     np.testing.assert_allclose(P[:8], erqw[f"{tag}_P_head"], rtol=0, atol=1e-13 * f)
     np.testing.assert_allclose(P.sum(axis=0), erqw[f"{tag}_P_colsum"], rtol=0, atol=1e-12 * f ** 1.5)
     return _sha(P) == str(erqw[f"{tag}_P_sha"])
-
-
-def _assert_ties_only(got, ref, X, c, P, lv, nbits, max_frac=1e-3):
-    """Index mismatches only where s sits on a level midpoint (fp64 rounding), one level apart."""
-    N, D = X.shape
-    gi, ri = _erq_unpack(got, D, nbits), _erq_unpack(ref, D, nbits)
-    bad = np.argwhere(gi != ri)
-    r = X.astype(np.float64) - c
-    s = (r / np.maximum(np.linalg.norm(r, axis=1), 1e-12)[:, None] @ P) * np.sqrt(D)
-    mids = 0.5 * (lv[:-1] + lv[1:])
-    for i, j in bad:
-        assert np.min(np.abs(mids - s[i, j])) <= 1e-12 * max(1.0, abs(s[i, j])), (i, j)
-        assert abs(int(gi[i, j]) - int(ri[i, j])) == 1
-    assert len(bad) <= max_frac * N * D
-    return bad
 
 
 def test_extrabitq_wide_oracle_matches_reference(oracle, erqw, mk):

@@ -490,12 +490,19 @@ def rabitq_code_size(d: int) -> int:
     return (d + 7) // 8 + 8
 
 
-def rabitq_encode(x: torch.Tensor, centroid: Optional[torch.Tensor], metric: int) -> torch.Tensor:
+def rabitq_encode(x: torch.Tensor, centroid: Optional[torch.Tensor], metric: int,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _check(x, "x", torch.float32, 2)
+    n, d = x.shape
     if centroid is not None:
         _check(centroid, "centroid", torch.float32, 1)
-    n, d = x.shape
-    out = torch.empty((n, rabitq_code_size(d)), dtype=torch.uint8, device=x.device)
+    cs = rabitq_code_size(d)
+    if out is None:
+        out = torch.empty((n, cs), dtype=torch.uint8, device=x.device)
+    else:
+        _check(out, "out", torch.uint8, 2)
+        if tuple(out.shape) != (n, cs):
+            raise ValueError(f"out shape {tuple(out.shape)} != {(n, cs)}")
     _call("mivq_rabitq_encode", _ptr(x), n, d, _ptr(centroid), metric, _ptr(out), _stream())
     return out
 
@@ -558,29 +565,62 @@ def extrabitq_code_size(d: int, nbits: int) -> int:
     return (d * nbits + 7) // 8 + 8
 
 
-def extrabitq_encode(x: torch.Tensor, c: torch.Tensor, P: torch.Tensor, levels: torch.Tensor,
-                     nbits: int) -> torch.Tensor:
-    """Codes of ExtendedRaBitQuantizer.compress (the o . P rotation on gemm_f64)."""
-    if x.dtype not in (torch.float32, torch.float64):
-        raise ValueError(f"extrabitq: unsupported dtype {x.dtype}")
+def _extrabitq_bits_check(nbits: int) -> None:
+    if nbits not in range(1, 9):
+        raise ValueError(f"num_bits must be in [1, 8], got {nbits}")
+
+
+def extrabitq_normalize(x: torch.Tensor, c: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(o (n, d) f64, nrm (n,) f64) of mivq_extrabitq_normalize: r = x - c, nrm = ||r||,
+    o = r / max(nrm, 1e-12); x is f32 or f64 rows."""
+    if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"extrabitq: unsupported dtype {getattr(x, 'dtype', type(x))}")
     _check(x, "x", x.dtype, 2)
-    for t, nm in ((c, "c"), (levels, "levels")):
-        _check(t, nm, torch.float64, 1)
-    _check(P, "P", torch.float64, 2)
+    _check(c, "c", torch.float64, 1)
     n, d = x.shape
+    if c.numel() != d:
+        raise ValueError(f"extrabitq: c has {c.numel()} entries, data has d={d}")
     o = torch.empty((n, d), dtype=torch.float64, device=x.device)
     nrm = torch.empty((n,), dtype=torch.float64, device=x.device)
     _call("mivq_extrabitq_normalize", _ptr(x), 1 if x.dtype == torch.float64 else 0, n, d, _ptr(c), _ptr(o),
           _ptr(nrm), _stream())
-    s_raw = gemm_f64(o, P, False)
-    codes = torch.empty((n, extrabitq_code_size(d, nbits)), dtype=torch.uint8, device=x.device)
-    _call("mivq_extrabitq_quantize", _ptr(s_raw), n, d, _ptr(levels), nbits, _ptr(nrm), _ptr(codes), _stream())
-    return codes
+    return o, nrm
+
+
+def extrabitq_quantize(s_raw: torch.Tensor, levels: torch.Tensor, nbits: int, nrm: torch.Tensor,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Code rows (n, code_size) u8 of mivq_extrabitq_quantize from the rotated unit rows
+    s_raw = o . P (n, d) f64 and their norms: the B-bit level indices of s_raw * sqrt(d), MSB-first,
+    then f32 nrm and f32 t."""
+    _extrabitq_bits_check(nbits)
+    _check(s_raw, "s_raw", torch.float64, 2)
+    _check(levels, "levels", torch.float64, 1)
+    _check(nrm, "nrm", torch.float64, 1)
+    n, d = s_raw.shape
+    if levels.numel() != 1 << nbits:
+        raise ValueError(f"extrabitq: levels has {levels.numel()} entries, expected {1 << nbits}")
+    if nrm.numel() != n:
+        raise ValueError(f"extrabitq: nrm has {nrm.numel()} entries, data has n={n}")
+    cs = extrabitq_code_size(d, nbits)
+    if out is None:
+        out = torch.empty((n, cs), dtype=torch.uint8, device=s_raw.device)
+    else:
+        _check(out, "out", torch.uint8, 2)
+        if tuple(out.shape) != (n, cs):
+            raise ValueError(f"out shape {tuple(out.shape)} != {(n, cs)}")
+    _call("mivq_extrabitq_quantize", _ptr(s_raw), n, d, _ptr(levels), nbits, _ptr(nrm), _ptr(out), _stream())
+    return out
+
+
+def extrabitq_encode(x: torch.Tensor, c: torch.Tensor, P: torch.Tensor, levels: torch.Tensor,
+                     nbits: int) -> torch.Tensor:
+    """Codes of ExtendedRaBitQuantizer.compress (the o . P rotation on gemm_f64)."""
+    o, nrm = extrabitq_normalize(x, c)
+    return extrabitq_quantize(gemm_f64(o, P, False), levels, nbits, nrm)
 
 
 def _extrabitq_code_check(codes: torch.Tensor, d: int, nbits: int, what: str) -> None:
-    if nbits not in range(1, 9):
-        raise ValueError(f"num_bits must be in [1, 8], got {nbits}")
+    _extrabitq_bits_check(nbits)
     if not isinstance(codes, torch.Tensor) or codes.dtype != torch.uint8 or codes.dim() != 2:
         raise ValueError(f"{what}: codes must be a 2-D uint8 tensor, got "
                          f"{tuple(getattr(codes, 'shape', ()))} {getattr(codes, 'dtype', type(codes))}")
@@ -602,15 +642,25 @@ def extrabitq_dequantize(codes: torch.Tensor, levels: torch.Tensor, nbits: int, 
     return o_hat
 
 
-def extrabitq_decode(codes: torch.Tensor, c: torch.Tensor, P: torch.Tensor, levels: torch.Tensor,
-                     nbits: int) -> torch.Tensor:
-    _check(codes, "codes", torch.uint8, 2)
-    n = codes.shape[0]
-    d = P.shape[0]
-    y = gemm_f64(extrabitq_dequantize(codes, levels, nbits, d), P, True)
-    out = torch.empty((n, d), dtype=torch.float32, device=codes.device)
+def extrabitq_finish(y: torch.Tensor, codes: torch.Tensor, c: torch.Tensor, nbits: int) -> torch.Tensor:
+    """(n, d) f32 of mivq_extrabitq_finish: f32(y * nrm + c), y = o_hat . P^T (n, d) f64 and nrm the
+    f32 norm stored in each code row."""
+    _check(y, "y", torch.float64, 2)
+    n, d = y.shape
+    _extrabitq_code_check(codes, d, nbits, "extrabitq_finish")
+    _check(c, "c", torch.float64, 1)
+    if codes.shape[0] != n or c.numel() != d:
+        raise ValueError(f"extrabitq_finish: {codes.shape[0]} code rows / c of {c.numel()} for y {tuple(y.shape)}")
+    out = torch.empty((n, d), dtype=torch.float32, device=y.device)
     _call("mivq_extrabitq_finish", _ptr(y), n, d, _ptr(codes), nbits, _ptr(c), _ptr(out), _stream())
     return out
+
+
+def extrabitq_decode(codes: torch.Tensor, c: torch.Tensor, P: torch.Tensor, levels: torch.Tensor,
+                     nbits: int) -> torch.Tensor:
+    _check(P, "P", torch.float64, 2)
+    y = gemm_f64(extrabitq_dequantize(codes, levels, nbits, P.shape[0]), P, True)
+    return extrabitq_finish(y, codes, c, nbits)
 
 
 def extrabitq_flat_search(qy: torch.Tensor, codes: torch.Tensor, levels: torch.Tensor, nbits: int, k: int,
