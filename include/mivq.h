@@ -520,6 +520,59 @@ int mivq_ivf_lvq_search(const float* q, int64_t nq, int32_t d, const float* coar
                         int32_t nbits, int32_t metric, int32_t k, void* workspace,
                         size_t workspace_bytes, float* dists, uint32_t* ids, void* stream);
 
+/* ------------------------------------------------------ IVF with a PQ codebook per list
+ * GPU counterpart of IvfQuantizedIndex (methods/search/ivf_quantized_index.py) around a
+ * ProductQuantizer per list, each fitted on its own list's residuals (run_benchmarks' pq_ivf).
+ * A row i belongs to list l = assign[i], whose centroid is c = coarse[l]; cb is the
+ * (nlist, M, ksub, dsub) array of per-list codebooks, ksub = 2^nbits, dsub = d / M.  All
+ * operations are fp32 with one rounding per step:
+ *   residual      r_t = x_t - c_t                                  (mivq_ivf_residuals)
+ *   fit, list l   cb[l] = train_pq(R_l, M, nbits, niter, seed) on the list's residuals R_l in
+ *                 ascending row order; an empty list keeps zeros and is never read
+ *   code row      mivq_pq_encode(R_l, cb[l]) of the row, stored one byte per sub-code (nbits < 8:
+ *                 mivq_pq_unpack), i.e. list_codes (N, M) u8 in bucket order
+ *   x^            e[m][j][t] = cb[l][m][j][t] + c[m*dsub + t]        (one add)
+ *                 x^_{m*dsub+t} = e[m][code_m][t]                    (= mivq_pq_decode + c)
+ *   table         T[m][j] = fmaf chain over t ascending of (q_{m*dsub+t} - e[m][j][t])^2        (L2)
+ *                 T[m][j] = -(fmaf chain over t ascending of q_{m*dsub+t} * e[m][j][t])         (IP)
+ *   key           ((T[0][code_0] + T[1][code_1]) + ...) + T[M-1][code_{M-1}]
+ * By construction T is mivq_adc_lut(q, e, metric), and the key is mivq_adc_search's sum over the
+ * list's codes.  The table is built on e = cb + c, not on the query residual q - c: the key is
+ * the ADC distance to the reconstruction x^ (the reference's distance to decompress(codes) +
+ * centroid, up to the fp32 reordering documented for mivq_adc_search).
+ * There is no fit entry point: the fit is train_pq per list on the host side of the package.
+ * mivq_ivf_listpq_decode writes x^ for rows in any order (codes (n, M) u8, assign (n,));
+ * assign[i] >= nlist is undefined behaviour, a sub-code >= ksub is taken modulo ksub. */
+int mivq_ivf_listpq_decode(const uint8_t* codes, int64_t n, int32_t d, int32_t M, int32_t nbits,
+                           const float* codebooks, const float* coarse, int32_t nlist,
+                           const uint32_t* assign, float* out, void* stream);
+/* ADC search over the probed lists.  probe_l (nq, nprobe): list ids; offsets (nlist + 1) int64,
+ * list_codes (n, M) u8, list_ids (n,) in bucket order, codebooks (nlist, M, ksub, dsub), coarse
+ * (nlist, d), all on the device.  The result for a query is defined over the rows of its probed
+ * lists: it holds the k smallest (key, id) over those rows, ascending; id is the list_ids entry
+ * compared as uint32; a NaN key ranks as +inf; it is padded with (+inf, 0xFFFFFFFF) after every
+ * real row; it is independent of the order of the probe slots; slots holding 0xFFFFFFFF or any
+ * id >= nlist are skipped (a query's live slots name distinct lists).  This equals bit for bit
+ * the composition: for every probed list, mivq_adc_lut on the shifted codebook e and
+ * mivq_adc_search on that list's codes, merged by (dist, id).
+ * Limits, checked on the host before any launch.  MIVQ_ERR_UNSUPPORTED: k outside [1, 256];
+ * nlist > 16383; an unknown metric.  MIVQ_ERR_INVALID: d % M != 0; nbits outside [1, 8]; bad
+ * sizes (d > 2^20 among them); null pointers.  Every M that divides d works, dsub = 1 included:
+ * the tables are staged into LDS in chunks of subspaces, there is no M * ksub * 4 <= LDS limit.
+ * nq = 0 and n = 0 return MIVQ_OK.  Stream-ordered, no host synchronisation.  The workspace
+ * holds one M * ksub * 4 byte table per (query, probe slot) pair of a chunk of queries; its
+ * size depends on the shape alone and is 0 for invalid sizes.  Queries go through in chunks
+ * sized so that the workspace aims at 512 MiB and stays under 1 GiB; at large M * nprobe a
+ * chunk holds few queries (one at the least: nprobe * M * ksub * 4 bytes are always needed). */
+size_t mivq_ivf_listpq_search_workspace_bytes(int64_t nq, int64_t n, int32_t nlist, int32_t nprobe,
+                                              int32_t d, int32_t M, int32_t nbits, int32_t k);
+int mivq_ivf_listpq_search(const float* q, int64_t nq, int32_t d, int32_t M, int32_t nbits,
+                           const float* codebooks, const float* coarse, int32_t nlist,
+                           const uint32_t* probe_l, int32_t nprobe, const int64_t* offsets,
+                           const uint8_t* list_codes, const uint32_t* list_ids, int32_t metric,
+                           int32_t k, void* workspace, size_t workspace_bytes, float* dists,
+                           uint32_t* ids, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

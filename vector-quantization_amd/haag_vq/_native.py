@@ -129,6 +129,10 @@ SIGNATURES = {
     "mivq_ivf_lvq_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32, _i32, _i32]),
     "mivq_ivf_lvq_search": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
                                        _vp, _sz, _vp, _vp, _vp]),
+    "mivq_ivf_listpq_decode": (_c.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "mivq_ivf_listpq_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "mivq_ivf_listpq_search": (_c.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32,
+                                          _i32, _vp, _sz, _vp, _vp, _vp]),
 }
 
 ABI_VERSION = 2  # MIVQ_ABI_VERSION of include/mivq.h the table above binds
@@ -1336,3 +1340,59 @@ def ivf_code_search(kind: str, q: torch.Tensor, coarse: torch.Tensor, probe_l: t
     _ivf_code_check(coarse, None, tuple(zip(names, params)), list_codes.shape[0], d, "ivf_code_search")
     return _ivf_list_search(kind, "ivf_code_search", q, coarse, probe_l, offsets, list_codes, list_ids, (nbits,),
                             (*[_ptr(t) for t in params], nbits), metric, k)
+
+
+# ----------------------------------------------------------------- IVF with a PQ codebook per list
+def _ivf_listpq_check(codes: torch.Tensor, codebooks: torch.Tensor, coarse: torch.Tensor, nbits: int, what: str) -> int:
+    """Shapes of (n, M) u8 codes, (nlist, M, 2^nbits, dsub) codebooks and (nlist, d) centroids; returns d."""
+    _check(codes, "codes", torch.uint8, 2)
+    _check(codebooks, "codebooks", torch.float32, 4)
+    _check(coarse, "coarse", torch.float32, 2)
+    nlist, M, ksub, dsub = codebooks.shape
+    if not 1 <= nbits <= 8:
+        raise ValueError(f"{what}: nbits={nbits} not in [1, 8]")
+    if ksub != 1 << nbits or codes.shape[1] != M or tuple(coarse.shape) != (nlist, M * dsub):
+        raise ValueError(f"{what}: codes {tuple(codes.shape)}, codebooks {tuple(codebooks.shape)} and coarse "
+                         f"{tuple(coarse.shape)} do not match at nbits={nbits}")
+    return M * dsub
+
+
+def ivf_listpq_decode(codes: torch.Tensor, codebooks: torch.Tensor, coarse: torch.Tensor, assign: torch.Tensor,
+                      nbits: int) -> torch.Tensor:
+    """x^ (n, d) f32: pq_decode(row, codebooks[l]) + coarse[l], l = assign[i]; codes (n, M) one byte
+    per sub-code, rows in any order."""
+    d = _ivf_listpq_check(codes, codebooks, coarse, nbits, "ivf_listpq_decode")
+    _check(assign, "assign", torch.int32, 1)
+    n = codes.shape[0]
+    if assign.shape[0] != n:
+        raise ValueError("ivf_listpq_decode: shape mismatch")
+    out = torch.empty((n, d), dtype=torch.float32, device=codes.device)
+    _call("mivq_ivf_listpq_decode", _ptr(codes), n, d, codebooks.shape[1], nbits, _ptr(codebooks), _ptr(coarse),
+          coarse.shape[0], _ptr(assign), _ptr(out), _stream())
+    return out
+
+
+def ivf_listpq_search(q: torch.Tensor, codebooks: torch.Tensor, coarse: torch.Tensor, probe_l: torch.Tensor,
+                      offsets: torch.Tensor, list_codes: torch.Tensor, list_ids: torch.Tensor, nbits: int, metric: int,
+                      k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ADC search over the probed lists of an IVF with one PQ codebook per list: (keys f32 (nq, k),
+    ids int32 (nq, k) holding uint32 ids), ascending; IP keys are negated inner products; missing
+    slots hold (+inf, 0xFFFFFFFF).  Bit-identical to adc_lut(q, codebooks[l] + coarse[l]) +
+    adc_search over every probed list, merged by (key, id)."""
+    _check(q, "q", torch.float32, 2)
+    d = _ivf_listpq_check(list_codes, codebooks, coarse, nbits, "ivf_listpq_search")
+    _check(probe_l, "probe_l", torch.int32, 2)
+    _check(offsets, "offsets", torch.int64, 1)
+    _check(list_ids, "list_ids", torch.int32, 1)
+    nq = q.shape[0]
+    nlist, M = codebooks.shape[0], codebooks.shape[1]
+    n, nprobe = list_codes.shape[0], probe_l.shape[1]
+    if q.shape[1] != d or probe_l.shape[0] != nq or offsets.shape[0] != nlist + 1 or list_ids.shape[0] != n:
+        raise ValueError("ivf_listpq_search: shape mismatch")
+    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+    ws = workspace(load_library().mivq_ivf_listpq_search_workspace_bytes(nq, n, nlist, nprobe, d, M, nbits, k), q.device)
+    _call("mivq_ivf_listpq_search", _ptr(q), nq, d, M, nbits, _ptr(codebooks), _ptr(coarse), nlist, _ptr(probe_l), nprobe,
+          _ptr(offsets), _ptr(list_codes), _ptr(list_ids), metric, k, _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids),
+          _stream())
+    return dists, ids

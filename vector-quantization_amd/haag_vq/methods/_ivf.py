@@ -21,6 +21,10 @@ of benchmarks/ivf_benchmark.py:170-204:
 * ``IvfCodes``  per-list SQ / LVQ codes of x - coarse[list(x)] (the reference's IvfQuantizedIndex:
   one quantizer per list, fitted on the list's residuals): the parameters of all lists as
   (nlist, d) tensors, lists in bucket order, and the exact search over the probed lists.
+* ``IvfListPq``  one PQ codebook per list, trained on the list's residuals (the reference's
+  IvfQuantizedIndex around a ProductQuantizer, run_benchmarks' ``pq_ivf``): (nlist, M, ksub, dsub)
+  codebooks, lists in bucket order, and the ADC search whose lookup table belongs to a (query,
+  probed list) pair.
 
 faiss itself is absent here, so coarse centroids, codebooks and results are not claimed to
 equal faiss'; the arithmetic is the canonical one of include/mivq.h and oracle/.
@@ -328,3 +332,76 @@ class IvfCodes(_IvfEngine):
         L = self.lists
         return _native.ivf_code_search(self.kind, Q, self.coarse, self.probes(Q, nprobe), L.offsets, L.codes,
                                        L.ids, self.params, self.nbits, self.metric, k)
+
+
+def short_list_error(counts: np.ndarray, nbits: int) -> Optional[str]:
+    """The message for lists that hold rows, but fewer than the 2^nbits a codebook is trained on
+    (None when there is none); faiss' wording, as the reference's per-list fit raises it."""
+    ksub = 1 << nbits
+    short = np.flatnonzero((counts > 0) & (counts < ksub))
+    if short.size == 0:
+        return None
+    l = int(short[0])
+    return (f"Number of training points ({int(counts[l])}) should be at least as large as number of clusters ({ksub}): "
+            f"list {l} of {counts.size} ({short.size} non-empty list{'s hold' if short.size > 1 else ' holds'} fewer than "
+            f"{ksub} rows); use a smaller K or B")
+
+
+class IvfListPq(_IvfEngine):
+    """IVF with one PQ codebook per list, fitted on the list's residuals (device-resident); the
+    engine behind IvfListPqIndex.  ``codebooks`` is (K, M, ksub, dsub) f32 (zeros for an empty
+    list), the lists hold (N, M) uint8 codes in bucket order, ``pos[id]`` is the bucket position
+    of row ``id``.  ``fit_lists`` trains the K codebooks one after the other (a host loop)."""
+
+    def __init__(self, d: int, K: int, M: int, nbits: int = 8, metric: int = _native.METRIC_L2, niter: int = 25,
+                 seed: int = 1234) -> None:
+        if d % M != 0:
+            raise AssertionError("D must be divisible by M (number of subquantizers)")
+        super().__init__(d, K, metric)
+        self.M, self.nbits, self.niter, self.seed = int(M), int(nbits), int(niter), int(seed)
+        self.codebooks: Optional[torch.Tensor] = None
+        self.pos: Optional[torch.Tensor] = None
+        self.list_of: Optional[torch.Tensor] = None
+
+    def fit_lists(self, X: torch.Tensor) -> None:
+        """Assign every row, train each non-empty list's codebook on its residuals (ascending
+        row order), encode them, and lay the lists out in bucket order (ids 0 .. N - 1).  A
+        non-empty list with fewer than 2^nbits rows raises before any training."""
+        a = self._assign(X)
+        offsets, order = _native.bucket_sort(a, self.K)
+        off = offsets.cpu().numpy()
+        msg = short_list_error(np.diff(off), self.nbits)
+        if msg is not None:
+            raise RuntimeError(msg)
+        n = X.shape[0]
+        ksub = 1 << self.nbits
+        cb = torch.zeros((self.K, self.M, ksub, self.d // self.M), dtype=torch.float32, device=X.device)
+        codes = torch.empty((n, self.M), dtype=torch.uint8, device=X.device)
+        for l in range(self.K):
+            b, e = int(off[l]), int(off[l + 1])
+            if e == b:
+                continue
+            rows = order[b:e].contiguous()
+            R = _native.ivf_residuals(_native.gather_rows(X, rows), self.coarse, a[rows.long()].contiguous())
+            C = train_pq(R, self.M, self.nbits, niter=self.niter, seed=self.seed)
+            cb[l] = C
+            c = _native.pq_encode(R, C, _native.pq_prepare(C, self.nbits), self.nbits)
+            codes[b:e] = c if self.nbits == 8 else _native.pq_unpack(c, self.M, self.nbits)
+        self.codebooks = cb
+        self.lists = IvfLists(offsets=offsets, codes=codes, ids=order.clone(), tau=None)
+        self.ntotal = n
+        self._index_rows()
+
+    _index_rows = IvfCodes._index_rows
+
+    def reconstruct(self, rows: torch.Tensor) -> torch.Tensor:
+        """x^ (len(rows), d) f32 of the rows with these ids: pq_decode with the list's codebook + centroid."""
+        p = self.pos[rows.to(self.pos.device).long()]
+        return _native.ivf_listpq_decode(self.lists.codes[p].contiguous(), self.codebooks, self.coarse,
+                                         self.list_of[p].contiguous(), self.nbits)
+
+    def search(self, Q: torch.Tensor, k: int, nprobe: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(keys f32 (nq, k), ids int32 (nq, k)); L2 ascending, IP as negated inner products."""
+        L = self.lists
+        return _native.ivf_listpq_search(Q, self.codebooks, self.coarse, self.probes(Q, nprobe), L.offsets, L.codes,
+                                         L.ids, self.nbits, self.metric, k)

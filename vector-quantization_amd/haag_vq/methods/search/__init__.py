@@ -1,9 +1,10 @@
 from .faiss_ivfpq_index import FaissIvfPqIndex
 from .flat_quantized_index import (ExtendedRaBitQFlatIndex, FlatQuantizedIndex, FlatADCIndex, RankAwareFlatIndex,
                                    search_codes)
+from .ivf_listpq_index import IvfListPqIndex
 from .ivf_quantized_index import IvfQuantizedIndex
 from .rabitq_index import RaBitQIndex
 from .rabitq_ivf_index import RaBitQIVFIndex
 
 __all__ = ["FaissIvfPqIndex", "FlatQuantizedIndex", "FlatADCIndex", "RankAwareFlatIndex", "ExtendedRaBitQFlatIndex",
-           "IvfQuantizedIndex", "RaBitQIndex", "RaBitQIVFIndex", "search_codes"]
+           "IvfQuantizedIndex", "IvfListPqIndex", "RaBitQIndex", "RaBitQIVFIndex", "search_codes"]

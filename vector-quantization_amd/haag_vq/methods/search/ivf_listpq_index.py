@@ -1,19 +1,27 @@
-"""IvfQuantizedIndex — a k-means IVF shell around per-list SQ / LVQ quantizers, on the MI355X.
+"""IvfListPqIndex — a k-means IVF shell around one product quantizer per list, on the MI355X.
 
-Drop-in for the reference's ``IvfQuantizedIndex`` (methods/search/ivf_quantized_index.py): fit
-trains ``K`` coarse centroids, assigns every row to its nearest one and fits one quantizer per
-list on that list's residuals x - centroid; search decodes the rows of the ``nprobe`` nearest
-lists, adds each list's centroid back and ranks by the exact distance to the reconstruction.
+Drop-in for the reference's ``IvfQuantizedIndex`` (methods/search/ivf_quantized_index.py) when its
+factory returns a ``ProductQuantizer`` — the ``pq_ivf`` method of run_benchmarks: fit trains ``K``
+coarse centroids, assigns every row to its nearest one and trains one PQ codebook per list on that
+list's residuals x - centroid; search ranks the rows of the ``nprobe`` nearest lists by the
+distance to decompress(codes) + centroid.  The constructor is the reference's, so a caller of the
+reference changes only the class name (this package's ``IvfQuantizedIndex`` stays native for SQ
+and LVQ and refuses PQ).
 
-Native for factories that return this package's ``ScalarQuantizer`` (4 / 8 / 16 bits, f32) or
-``LVQQuantizer`` (1..8 bits); the factory is called once, to learn the kind and the bits, and
-any other quantizer raises ``NotImplementedError`` (a ``ProductQuantizer`` per list is
-``IvfListPqIndex``, ivf_listpq_index.py).  The coarse
-quantizer and the lists are the ones of ``FaissIvfPqIndex`` (``_ivf.train_coarse``, bucket
-order), the per-list parameters are (K, d) tensors, and no list is decoded to memory: the
-search is ``mivq_ivf_sq_search`` / ``mivq_ivf_lvq_search`` (include/mivq.h), bit-identical to
-decode + add + ``mivq_flat_search`` over the probed rows.  faiss is absent, so the centroids
-are not claimed to equal faiss'.
+The factory is called once and must return this package's ``ProductQuantizer``; its ``M``, ``B``,
+``niter`` and ``seed`` serve every list (the reference calls the factory per list; every instance
+has the same settings).  The coarse quantizer and the lists are the ones of ``FaissIvfPqIndex``
+(``_ivf.train_coarse``, bucket order); the codebooks are one (K, M, 2^B, D/M) tensor, each list's
+trained by ``_kmeans.train_pq`` on its residuals.  No list is decoded: the search is
+``mivq_ivf_listpq_search`` (include/mivq.h), an ADC whose lookup table belongs to a (query,
+probed list) pair and is built on codebook + centroid, so the key is the ADC distance to the
+reconstruction ``reconstruct`` returns — the reference's exact distance up to the fp32 reordering
+``FlatQuantizedIndex`` documents for PQ.  faiss is absent, so neither centroids nor codebooks are
+claimed to equal faiss'.
+
+As in the reference (faiss refuses to train 2^B centroids on fewer points), a fit in which a
+non-empty list holds fewer than 2^B rows raises; here all lists are checked right after the
+assignment, before any training.  Empty lists are skipped.
 
 ``search_with_scores`` returns what the reference returns: ``(ids uint32, dists float32)`` of
 shape (nq, k) always, ascending; for ``'ip'`` the negated inner products; slots the probed lists
@@ -30,7 +38,7 @@ import numpy as np
 import torch
 
 from ... import _arrays, _native
-from .._ivf import IvfCodes, IvfLists
+from .._ivf import IvfListPq, IvfLists
 from ..base_quantizer import BaseQuantizer
 from ..base_search_index import BaseSearchIndex
 
@@ -40,30 +48,23 @@ _FLT_MAX = np.finfo(np.float32).max
 _DECODE_BYTES = 1 << 28  # reconstruction_mse: decoded rows per step
 
 
-def _kind_of(q) -> Tuple[str, int]:
-    from ..lvq_quantization import LVQQuantizer
-    from ..scalar_quantization import ScalarQuantizer
-
-    if isinstance(q, ScalarQuantizer):
-        return "sq", int(q.num_bits)
-    if isinstance(q, LVQQuantizer):
-        return "lvq", int(q.num_bits)
-    raise NotImplementedError(
-        f"IvfQuantizedIndex is native for ScalarQuantizer (4 / 8 / 16 bits) and LVQQuantizer (1..8 bits); "
-        f"the factory returned {type(q).__name__}")
-
-
-class IvfQuantizedIndex(BaseSearchIndex):
-    """IVF + per-list quantization: ``K`` coarse cells, ``nprobe`` of them scanned per query."""
+class IvfListPqIndex(BaseSearchIndex):
+    """IVF + one PQ codebook per list: ``K`` coarse cells, ``nprobe`` of them scanned per query."""
 
     def __init__(self, quantizer_factory: Callable[[], BaseQuantizer], K: int = 4096, nprobe: int = 200) -> None:
+        from ..product_quantization import ProductQuantizer
+
         self._quantizer_factory = quantizer_factory
-        self._kind, self._bits = _kind_of(quantizer_factory())
+        q = quantizer_factory()
+        if not isinstance(q, ProductQuantizer):
+            raise ValueError(f"IvfListPqIndex needs a factory of ProductQuantizer; it returned {type(q).__name__} "
+                             f"(per-list SQ / LVQ: IvfQuantizedIndex)")
+        self._M, self._B, self._niter, self._seed = int(q.M), int(q.B), int(q.niter), int(q.seed)
         self._K = int(K)
         self._nprobe = int(nprobe)
         if self._K <= 0 or self._nprobe <= 0:
             raise ValueError(f"K and nprobe must be positive, got {K}, {nprobe}")
-        self._index: Optional[IvfCodes] = None
+        self._index: Optional[IvfListPq] = None
         self._metric: Literal["l2", "ip"] = "l2"
         self._N: int = 0
         self._D: int = 0
@@ -86,7 +87,7 @@ class IvfQuantizedIndex(BaseSearchIndex):
             raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
         Xd = _arrays.to_device(X, torch.float32)
         n, d = int(Xd.shape[0]), int(Xd.shape[1])
-        index = IvfCodes(d, self._K, self._kind, self._bits, _METRIC[metric])
+        index = IvfListPq(d, self._K, self._M, self._B, _METRIC[metric], niter=self._niter, seed=self._seed)
         if centroids is None:
             index.train(Xd)
         else:
@@ -96,9 +97,9 @@ class IvfQuantizedIndex(BaseSearchIndex):
         index.fit_lists(Xd)
         self._index, self._metric, self._N, self._D = index, metric, n, d
 
-    def _require_fit(self) -> IvfCodes:
+    def _require_fit(self) -> IvfListPq:
         if self._index is None or self._index.lists is None:
-            raise RuntimeError("IvfQuantizedIndex must be fit() before use.")
+            raise RuntimeError("IvfListPqIndex must be fit() before use.")
         return self._index
 
     def _check_limits(self, k: int) -> None:
@@ -134,14 +135,13 @@ class IvfQuantizedIndex(BaseSearchIndex):
         return ids, dists
 
     def memory_footprint(self) -> int:
-        """The reference's formula (centroid bytes + code bytes) plus the per-list parameters
-        ((K, d) f32: lo and den for SQ, mu for LVQ), which the reference keeps in its quantizer
-        objects and does not count."""
+        """The reference's formula (centroid bytes + code bytes) plus the codebook bytes
+        K * D * 2^B * 4, which the reference keeps in its quantizer objects and does not count.
+        The codebooks dominate at many lists: 1 GiB at K = 1024, D = 1024, B = 8."""
         if self._index is None or self._index.lists is None:
             return 0
         codes = self._index.lists.codes
-        params = sum(t.numel() * t.element_size() for t in self._index.params)
-        return self._K * self._D * 4 + codes.numel() * codes.element_size() + params
+        return self._K * self._D * 4 + codes.numel() * codes.element_size() + self._K * self._D * (1 << self._B) * 4
 
     def reconstruction_mse(self, X, sample_ids: Optional[np.ndarray] = None) -> Optional[float]:
         if self._index is None or self._index.lists is None:
@@ -163,30 +163,30 @@ class IvfQuantizedIndex(BaseSearchIndex):
 
     def save(self, path: str | Path) -> None:
         if self._index is None or self._index.lists is None:
-            raise RuntimeError("IvfQuantizedIndex.save() called before fit()")
+            raise RuntimeError("IvfListPqIndex.save() called before fit()")
         path = Path(path)
         path.parent.mkdir(parents=True, exist_ok=True)
         ix, L = self._index, self._index.lists
-        arrays = {f"param{i}": _arrays.to_host(t) for i, t in enumerate(ix.params)}
         with open(path, "wb") as f:
-            np.savez(f, coarse=_arrays.to_host(ix.coarse), offsets=_arrays.to_host(L.offsets),
-                     codes=_arrays.to_host(L.codes), ids=_arrays.to_host(L.ids), kind=np.array(self._kind),
-                     bits=np.array(self._bits), K=np.array(self._K), nprobe=np.array(self._nprobe),
-                     metric=np.array(self._metric), N=np.array(self._N), D=np.array(self._D), **arrays)
+            np.savez(f, coarse=_arrays.to_host(ix.coarse), codebooks=_arrays.to_host(ix.codebooks),
+                     offsets=_arrays.to_host(L.offsets), codes=_arrays.to_host(L.codes), ids=_arrays.to_host(L.ids),
+                     M=np.array(self._M), B=np.array(self._B), niter=np.array(self._niter), seed=np.array(self._seed),
+                     K=np.array(self._K), nprobe=np.array(self._nprobe), metric=np.array(self._metric),
+                     N=np.array(self._N), D=np.array(self._D))
 
     def load(self, path: str | Path) -> None:
         with np.load(Path(path), allow_pickle=False) as z:
-            self._kind, self._bits = str(z["kind"]), int(z["bits"])
+            self._M, self._B = int(z["M"]), int(z["B"])
+            self._niter, self._seed = int(z["niter"]), int(z["seed"])
             self._K, self._nprobe = int(z["K"]), int(z["nprobe"])
             self._metric = str(z["metric"])
             self._N, self._D = int(z["N"]), int(z["D"])
-            index = IvfCodes(self._D, self._K, self._kind, self._bits, _METRIC[self._metric])
+            index = IvfListPq(self._D, self._K, self._M, self._B, _METRIC[self._metric], niter=self._niter,
+                              seed=self._seed)
             index.coarse = _arrays.to_device(np.array(z["coarse"]), torch.float32)
-            index.params = tuple(_arrays.to_device(np.array(z[f"param{i}"]), torch.float32)
-                                 for i in range(2 if self._kind == "sq" else 1))
-            codes = np.array(z["codes"])
+            index.codebooks = _arrays.to_device(np.array(z["codebooks"]), torch.float32)
             index.lists = IvfLists(offsets=_arrays.to_device(np.array(z["offsets"]), torch.int64),
-                                   codes=_arrays.to_device(codes, torch.int16 if codes.dtype.itemsize == 2 else torch.uint8),
+                                   codes=_arrays.to_device(np.array(z["codes"]), torch.uint8),
                                    ids=_arrays.to_device(np.array(z["ids"]), torch.int32), tau=None)
             index.ntotal = self._N
             index._index_rows()
