@@ -356,6 +356,46 @@ int mivq_lvq_flat_search(const float* q, int64_t nq, const uint8_t* codes, int64
                          const float* mu, int32_t nbits, int32_t metric, int32_t k,
                          int64_t id_offset, void* workspace, size_t workspace_bytes, float* dists,
                          uint32_t* ids, void* stream);
+/* Re-ranking: the exact searches above restricted, per query, to a list of candidate rows (the
+ * second stage of a two-stage search; faiss' IndexRefine).  cand is (nq, r) uint32 row-major on
+ * the device: the global ids a first stage returned for each query.  The store arguments are
+ * those of mivq_flat_search / mivq_sq_flat_search / mivq_lvq_flat_search: the same row formats,
+ * parameters and alignment freedom.
+ *   - the candidates of query a are the slots with id_offset <= cand[a][j] < id_offset + n, ids
+ *     compared as unsigned; every other slot is skipped, 0xFFFFFFFF (the padding the searches
+ *     write) among them;
+ *   - each live slot is a candidate of its own: duplicates are not removed (a repeated id may
+ *     appear twice in the output; callers pass distinct ids);
+ *   - dist(a, c) is the chain of the matching flat search for row c - id_offset, with x^_t as
+ *     that search dequantises it: L2 the fmaf chain over t ascending of (q_t - x^_t)^2, IP
+ *     -(fmaf chain of q_t * x^_t);
+ *   - out: the k smallest (dist, id) ascending, ties to the smaller id, NaN ranked and written as
+ *     +inf, missing slots (+inf, 0xFFFFFFFF).
+ * So dists are bit-identical to what mivq_*_flat_search reports for the same (query, row), and
+ * the result is the flat search's restricted to the candidate set.  No decoded row and no
+ * (nq, r, d) block is written anywhere: the workspace holds partial top-k lists only.
+ * Checked before any launch.  MIVQ_ERR_INVALID: nq < 0, n < 0, r < 1, d <= 0, ids that overflow
+ * 32 bits, 16-bit codes that are not 2-byte aligned, a null pointer with work to do.
+ * MIVQ_ERR_UNSUPPORTED: k outside [1, 256], an unknown metric, nbits outside {4, 8, 16} (SQ) /
+ * [1, 8] (LVQ), a d whose query and parameter rows (d rounded up to 4 floats each: f32 1, LVQ 2,
+ * SQ 3) exceed 160 KiB of LDS.  MIVQ_ERR_WORKSPACE: a workspace below the size query's.
+ * nq == 0 returns MIVQ_OK without a launch; n == 0 fills every row with the missing-slot
+ * values.  Stream-ordered, no host synchronisation. */
+size_t mivq_rerank_f32_workspace_bytes(int64_t nq, int64_t r, int32_t k);
+int mivq_rerank_f32(const float* q, int64_t nq, const uint32_t* cand, int64_t r, const float* x,
+                    int64_t n, int32_t d, int32_t metric, int32_t k, int64_t id_offset,
+                    void* workspace, size_t workspace_bytes, float* dists, uint32_t* ids,
+                    void* stream);
+size_t mivq_rerank_sq_workspace_bytes(int64_t nq, int64_t r, int32_t k);
+int mivq_rerank_sq(const float* q, int64_t nq, const uint32_t* cand, int64_t r, const void* codes,
+                   int64_t n, int32_t d, const float* lo, const float* den, int32_t nbits,
+                   int32_t metric, int32_t k, int64_t id_offset, void* workspace,
+                   size_t workspace_bytes, float* dists, uint32_t* ids, void* stream);
+size_t mivq_rerank_lvq_workspace_bytes(int64_t nq, int64_t r, int32_t k);
+int mivq_rerank_lvq(const float* q, int64_t nq, const uint32_t* cand, int64_t r,
+                    const uint8_t* codes, int64_t n, int32_t d, const float* mu, int32_t nbits,
+                    int32_t metric, int32_t k, int64_t id_offset, void* workspace,
+                    size_t workspace_bytes, float* dists, uint32_t* ids, void* stream);
 /* Merges `parts` sorted (nq, k) lists laid out (parts, nq, k) into one sorted (nq, k) list
  * with the same (dist, id) order (ids compared as uint32, NaN dists ranked and written as +inf)
  * — the on-device merge after the RCCL all-gather.  parts == 0 writes (+inf, 0xFFFFFFFF)

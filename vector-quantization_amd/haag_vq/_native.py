@@ -99,6 +99,14 @@ SIGNATURES = {
     "mivq_lvq_flat_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "mivq_lvq_flat_search": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i64, _vp, _sz, _vp, _vp,
                                         _vp]),
+    "mivq_rerank_f32_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "mivq_rerank_f32": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _sz, _vp, _vp, _vp]),
+    "mivq_rerank_sq_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "mivq_rerank_sq": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _sz, _vp,
+                                  _vp, _vp]),
+    "mivq_rerank_lvq_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "mivq_rerank_lvq": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i64, _vp, _sz, _vp, _vp,
+                                   _vp]),
     "mivq_extrabitq_flat_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "mivq_extrabitq_flat_search": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i64, _vp, _sz, _vp,
                                               _vp, _vp]),
@@ -1012,6 +1020,52 @@ def lvq_flat_search(q: torch.Tensor, codes: torch.Tensor, mu: torch.Tensor, nbit
     ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
     ws = workspace(load_library().mivq_lvq_flat_search_workspace_bytes(nq, n, d, k), q.device)
     _call("mivq_lvq_flat_search", _ptr(q), nq, _ptr(codes), n, d, _ptr(mu), nbits, metric, k, id_offset, _ptr(ws),
+          ws.numel(), _ptr(dists), _ptr(ids), _stream())
+    return dists, ids
+
+
+def rerank(kind: str, q: torch.Tensor, cand: torch.Tensor, store: torch.Tensor, params: Tuple[torch.Tensor, ...],
+           nbits: int, k: int, metric: int = METRIC_L2, id_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact top-k of every query among its own candidate rows (mivq_rerank_*): cand (nq, r) int32
+    holding the uint32 global ids a first stage returned; slots outside [id_offset, id_offset + n)
+    are skipped, the 0xFFFFFFFF padding among them.  store / params / nbits by kind: 'f32' the
+    (n, d) f32 rows, () and 0; 'sq' the code rows of sq_encode, (lo, den) and 4 / 8 / 16; 'lvq' the
+    code rows of lvq_encode, (mu,) and 1..8.  Returns (dists f32 (nq, k), ids int32 (nq, k) holding
+    uint32 ids), the rows the matching flat search reports for those candidates: ascending keys, IP
+    keys negated inner products, missing slots (+inf, 0xFFFFFFFF)."""
+    if kind not in ("f32", "sq", "lvq"):
+        raise ValueError(f"rerank: kind must be 'f32', 'sq' or 'lvq', got {kind!r}")
+    _check(q, "q", torch.float32, 2)
+    _check(cand, "cand", torch.int32, 2)
+    nq, d = q.shape
+    r = cand.shape[1]
+    if cand.shape[0] != nq:
+        raise ValueError(f"rerank: {cand.shape[0]} candidate lists for {nq} queries")
+    names = {"f32": (), "sq": ("lo", "den"), "lvq": ("mu",)}[kind]
+    if len(params) != len(names):
+        raise ValueError(f"rerank: {kind} takes the parameters {names}")
+    for name, t in zip(names, params):
+        _check(t, name, torch.float32, 1)
+        if t.numel() != d:
+            raise ValueError(f"rerank: {name} has {t.numel()} entries, expected d={d}")
+    if kind == "f32":
+        _check(store, "x", torch.float32, 2)
+        if store.shape[1] != d:
+            raise ValueError(f"database has d={store.shape[1]}, queries d={d}")
+        extra = ()
+    elif kind == "sq":
+        _sq_code_check(store, d, nbits, "rerank")
+        if not store.is_contiguous() or not store.is_cuda:
+            raise ValueError("codes must be a contiguous device tensor")
+        extra = (_ptr(params[0]), _ptr(params[1]), nbits)
+    else:
+        _lvq_code_check(store, d, nbits, "rerank")
+        extra = (_ptr(params[0]), nbits)
+    n = store.shape[0]
+    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+    ws = workspace(getattr(load_library(), f"mivq_rerank_{kind}_workspace_bytes")(nq, r, k), q.device)
+    _call(f"mivq_rerank_{kind}", _ptr(q), nq, _ptr(cand), r, _ptr(store), n, d, *extra, metric, k, id_offset, _ptr(ws),
           ws.numel(), _ptr(dists), _ptr(ids), _stream())
     return dists, ids
 

@@ -5,6 +5,7 @@ from .ivf_listpq_index import IvfListPqIndex
 from .ivf_quantized_index import IvfQuantizedIndex
 from .rabitq_index import RaBitQIndex
 from .rabitq_ivf_index import RaBitQIVFIndex
+from .refined_index import RefinedIndex
 
 __all__ = ["FaissIvfPqIndex", "FlatQuantizedIndex", "FlatADCIndex", "RankAwareFlatIndex", "ExtendedRaBitQFlatIndex",
-           "IvfQuantizedIndex", "IvfListPqIndex", "RaBitQIndex", "RaBitQIVFIndex", "search_codes"]
+           "IvfQuantizedIndex", "IvfListPqIndex", "RaBitQIndex", "RaBitQIVFIndex", "RefinedIndex", "search_codes"]
