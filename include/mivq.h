@@ -159,6 +159,28 @@ int mivq_lvq_encode(const float* x, int64_t n, int32_t d, const float* mu, int32
 int mivq_lvq_decode(const uint8_t* codes, int64_t n, int32_t d, const float* mu, int32_t nbits,
                     float* out, void* stream);
 
+/* ------------------------------------------------------ two-level LVQ (LVQ-B1xB2)
+ * A second level quantises what the first left over, on the interval the first level's step
+ * fixes, so it stores no constants of its own.  B1 = nbits1 in [1, 8] (else MIVQ_ERR_INVALID),
+ * B2 = nbits2 in {4, 8} (else MIVQ_ERR_UNSUPPORTED), L1 = 2^B1 - 1, L2 = 2^B2 - 1; fp32, one
+ * rounding per step, every division IEEE:
+ *   level 1: r_t, lo, delta, idx_t exactly as mivq_lvq_encode(x, ..., nbits1).
+ *   level 2: a_t = lo + (float)idx_t * delta, e_t = r_t - a_t, lo2 = -0.5f * delta,
+ *           delta2 = delta / (float)L2 (subnormal where delta is FLT_MIN: kept, not flushed),
+ *           j_t = clip((int)rint((e_t - lo2) / delta2), 0, L2), rint half to even.
+ *   codes1 = (n, ceil(d*B1/8) + 8): the rows of mivq_lvq_encode at nbits1, byte for byte.
+ *   codes2 = (n, ceil(d*B2/8)): j_t in bits [t*B2, (t+1)*B2) of the row's bit stream, MSB-first
+ *           from byte 0 (B2 = 4: the even dimension in the high nibble), padding bits 0, no
+ *           trailer.  Either array at any byte alignment.
+ *   decode: out_t = ((lo + (float)idx_t * delta) + (lo2 + (float)j_t * delta2)) + mu_t, lo2 and
+ *           delta2 recomputed from the row's delta.
+ * Inputs are finite; a row holding NaN encodes to unspecified bytes of its own two rows.  The
+ * other checks are those of mivq_lvq_encode / mivq_lvq_decode. */
+int mivq_lvq2_encode(const float* x, int64_t n, int32_t d, const float* mu, int32_t nbits1,
+                     int32_t nbits2, uint8_t* codes1, uint8_t* codes2, void* stream);
+int mivq_lvq2_decode(const uint8_t* codes1, const uint8_t* codes2, int64_t n, int32_t d,
+                     const float* mu, int32_t nbits1, int32_t nbits2, float* out, void* stream);
+
 /* ------------------------------------------------------ RaBitQ (1 bit)
  * Replaces faiss.RaBitQuantizer.compute_codes / decode (rabit_quantization.py:20-29).
  * Code row = ceil(d/8) sign bytes (bit j of dim j = (x_j - c_j) > 0, LSB-first) followed by
@@ -396,6 +418,19 @@ int mivq_rerank_lvq(const float* q, int64_t nq, const uint32_t* cand, int64_t r,
                     const uint8_t* codes, int64_t n, int32_t d, const float* mu, int32_t nbits,
                     int32_t metric, int32_t k, int64_t id_offset, void* workspace,
                     size_t workspace_bytes, float* dists, uint32_t* ids, void* stream);
+/* The same over two-level LVQ rows (mivq_lvq2_encode): the contract of mivq_rerank_lvq word for
+ * word, with x^_t the two-level reconstruction of mivq_lvq2_decode, so dists are bit-identical to
+ * mivq_lvq2_decode + mivq_flat_search for the same (query, row).  A unit of 32 dimensions is
+ * nbits1 words of codes1 and nbits2 words of codes2; each array is read with 8-byte (codes1, even
+ * nbits1) / 16-byte (codes2) loads, 4-byte loads or bytes, as its own base and row stride allow.
+ * nbits1 outside [1, 8] is MIVQ_ERR_INVALID, nbits2 outside {4, 8} MIVQ_ERR_UNSUPPORTED; the
+ * workspace is that of mivq_rerank_lvq. */
+size_t mivq_rerank_lvq2_workspace_bytes(int64_t nq, int64_t r, int32_t k);
+int mivq_rerank_lvq2(const float* q, int64_t nq, const uint32_t* cand, int64_t r,
+                     const uint8_t* codes1, const uint8_t* codes2, int64_t n, int32_t d,
+                     const float* mu, int32_t nbits1, int32_t nbits2, int32_t metric, int32_t k,
+                     int64_t id_offset, void* workspace, size_t workspace_bytes, float* dists,
+                     uint32_t* ids, void* stream);
 /* Merges `parts` sorted (nq, k) lists laid out (parts, nq, k) into one sorted (nq, k) list
  * with the same (dist, id) order (ids compared as uint32, NaN dists ranked and written as +inf)
  * — the on-device merge after the RCCL all-gather.  parts == 0 writes (+inf, 0xFFFFFFFF)

@@ -68,6 +68,8 @@ SIGNATURES = {
     "mivq_column_mean": (_c.c_int, [_vp, _i64, _i32, _vp, _vp]),
     "mivq_lvq_encode": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp]),
     "mivq_lvq_decode": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp]),
+    "mivq_lvq2_encode": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "mivq_lvq2_decode": (_c.c_int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp]),
     "mivq_rabitq_encode": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp]),
     "mivq_rabitq_decode": (_c.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
     "mivq_rabitq_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
@@ -107,6 +109,9 @@ SIGNATURES = {
     "mivq_rerank_lvq_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "mivq_rerank_lvq": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i64, _vp, _sz, _vp, _vp,
                                    _vp]),
+    "mivq_rerank_lvq2_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "mivq_rerank_lvq2": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i64, _vp,
+                                    _sz, _vp, _vp, _vp]),
     "mivq_extrabitq_flat_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "mivq_extrabitq_flat_search": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i64, _vp, _sz, _vp,
                                               _vp, _vp]),
@@ -494,6 +499,64 @@ def lvq_decode(codes: torch.Tensor, mu: torch.Tensor, nbits: int) -> torch.Tenso
     n = codes.shape[0]
     out = torch.empty((n, d), dtype=torch.float32, device=codes.device)
     _call("mivq_lvq_decode", _ptr(codes), n, d, _ptr(mu), nbits, _ptr(out), _stream())
+    return out
+
+
+# ----------------------------------------------------------------- two-level LVQ
+def _lvq2_bits_check(nbits1: int, nbits2: int) -> None:
+    if not 1 <= nbits1 <= 8:
+        raise ValueError(f"primary num_bits must be in [1, 8], got {nbits1}")
+    if nbits2 not in (4, 8):
+        raise ValueError(f"residual num_bits must be 4 or 8, got {nbits2}")
+
+
+def lvq2_code_sizes(d: int, nbits1: int, nbits2: int) -> Tuple[int, int]:
+    """Bytes per row of (codes1, codes2): the LVQ row at nbits1, and ceil(d nbits2 / 8) without a trailer."""
+    return lvq_code_size(d, nbits1), (d * nbits2 + 7) // 8
+
+
+def _lvq2_code_check(codes1: torch.Tensor, codes2: torch.Tensor, d: int, nbits1: int, nbits2: int, what: str) -> None:
+    _lvq2_bits_check(nbits1, nbits2)
+    for name, c, size in zip(("codes1", "codes2"), (codes1, codes2), lvq2_code_sizes(d, nbits1, nbits2)):
+        if not isinstance(c, torch.Tensor) or c.dtype != torch.uint8 or c.dim() != 2:
+            raise ValueError(f"{what}: {name} must be a 2-D uint8 tensor, got "
+                             f"{tuple(getattr(c, 'shape', ()))} {getattr(c, 'dtype', type(c))}")
+        if c.shape[1] != size:
+            raise ValueError(f"{name} has {c.shape[1]} bytes per row, expected {size}")
+        _check(c, name, torch.uint8, 2)
+    if codes1.shape[0] != codes2.shape[0]:
+        raise ValueError(f"{what}: codes1 has {codes1.shape[0]} rows, codes2 {codes2.shape[0]}")
+
+
+def lvq2_encode(x: torch.Tensor, mu: torch.Tensor, nbits1: int, nbits2: int, out1: Optional[torch.Tensor] = None,
+                out2: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(codes1, codes2) of mivq_lvq2_encode: codes1 is lvq_encode(x, mu, nbits1) byte for byte."""
+    _lvq2_bits_check(nbits1, nbits2)
+    _check(x, "x", torch.float32, 2)
+    _check(mu, "mu", torch.float32, 1)
+    n, d = x.shape
+    if mu.numel() != d:
+        raise ValueError(f"lvq2_encode: mu has {mu.numel()} entries, data has d={d}")
+    outs = []
+    for name, out, size in zip(("out1", "out2"), (out1, out2), lvq2_code_sizes(d, nbits1, nbits2)):
+        if out is None:
+            out = torch.empty((n, size), dtype=torch.uint8, device=x.device)
+        else:
+            _check(out, name, torch.uint8, 2)
+            if tuple(out.shape) != (n, size):
+                raise ValueError(f"{name} shape {tuple(out.shape)} != {(n, size)}")
+        outs.append(out)
+    _call("mivq_lvq2_encode", _ptr(x), n, d, _ptr(mu), nbits1, nbits2, _ptr(outs[0]), _ptr(outs[1]), _stream())
+    return outs[0], outs[1]
+
+
+def lvq2_decode(codes1: torch.Tensor, codes2: torch.Tensor, mu: torch.Tensor, nbits1: int, nbits2: int) -> torch.Tensor:
+    _check(mu, "mu", torch.float32, 1)
+    d = mu.numel()
+    _lvq2_code_check(codes1, codes2, d, nbits1, nbits2, "lvq2_decode")
+    n = codes1.shape[0]
+    out = torch.empty((n, d), dtype=torch.float32, device=codes1.device)
+    _call("mivq_lvq2_decode", _ptr(codes1), _ptr(codes2), n, d, _ptr(mu), nbits1, nbits2, _ptr(out), _stream())
     return out
 
 
@@ -1067,6 +1130,30 @@ def rerank(kind: str, q: torch.Tensor, cand: torch.Tensor, store: torch.Tensor, 
     ws = workspace(getattr(load_library(), f"mivq_rerank_{kind}_workspace_bytes")(nq, r, k), q.device)
     _call(f"mivq_rerank_{kind}", _ptr(q), nq, _ptr(cand), r, _ptr(store), n, d, *extra, metric, k, id_offset, _ptr(ws),
           ws.numel(), _ptr(dists), _ptr(ids), _stream())
+    return dists, ids
+
+
+def rerank_lvq2(q: torch.Tensor, cand: torch.Tensor, codes1: torch.Tensor, codes2: torch.Tensor, mu: torch.Tensor,
+                nbits1: int, nbits2: int, k: int, metric: int = METRIC_L2,
+                id_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """rerank() over the two arrays of lvq2_encode (mivq_rerank_lvq2): the keys are those of
+    flat_search(q, lvq2_decode(codes1, codes2)) for the candidates, bit for bit."""
+    _check(q, "q", torch.float32, 2)
+    _check(cand, "cand", torch.int32, 2)
+    _check(mu, "mu", torch.float32, 1)
+    nq, d = q.shape
+    r = cand.shape[1]
+    if cand.shape[0] != nq:
+        raise ValueError(f"rerank_lvq2: {cand.shape[0]} candidate lists for {nq} queries")
+    if mu.numel() != d:
+        raise ValueError(f"rerank_lvq2: mu has {mu.numel()} entries, expected d={d}")
+    _lvq2_code_check(codes1, codes2, d, nbits1, nbits2, "rerank_lvq2")
+    n = codes1.shape[0]
+    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+    ws = workspace(load_library().mivq_rerank_lvq2_workspace_bytes(nq, r, k), q.device)
+    _call("mivq_rerank_lvq2", _ptr(q), nq, _ptr(cand), r, _ptr(codes1), _ptr(codes2), n, d, _ptr(mu), nbits1, nbits2,
+          metric, k, id_offset, _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids), _stream())
     return dists, ids
 
 
