@@ -314,6 +314,48 @@ int mivq_rankaware_flat_search(const float* qy, int64_t nq, const uint8_t* codes
                                int32_t metric, int32_t k, int64_t id_offset, void* workspace,
                                size_t workspace_bytes, float* dists, uint32_t* ids, void* stream);
 
+/* Data-fitted level tables for the rank-aware format: per dimension, 2^width[j] levels fitted to
+ * that dimension's sample, by the globally optimal 1-D k-means (MIVQ_CB1D_EXACT, dynamic
+ * programming with divide and conquer, O(2^w n log n)) or by k-means++ seeding and at most 50
+ * Lloyd passes with empty-cell repair (MIVQ_CB1D_LLOYD).  Both are the sequential fp64 rule of
+ * tests/_codebook1d_rule.py bit for bit: prefix sums added in ascending order, every product and
+ * quotient rounded on its own, first minimum on ties.
+ *   cols   (d, n) f32, device: row j = dimension j's values, ascending
+ *   width  (d,)     int32, HOST: bits of dimension j, 0..8 (they size the launches)
+ *   lv_off (d + 1,) int32, HOST: start of dimension j's levels; lv_off[j + 1] - lv_off[j] = 2^width[j]
+ *   draws  (ndraws,) u64, device: the first raw outputs of the seeding's 64-bit generator
+ *          (mt19937_64(0) for the reference's tables), ndraws >= 2^max width; every dimension
+ *          reads them from the start.  Lloyd only; may be null for EXACT.
+ *   levels (lv_off[d],) f32, device: ascending; fewer distinct levels than 2^w (a dimension with
+ *          no more than 2^w distinct values gets exactly those) are padded with the last one
+ *   sse    (d,) f64, device: the table's sum of squared errors on the sample (0 when padded
+ *          because of too few distinct values)
+ * Dimensions of width 0 are skipped: their level and sse entries are not written.  One workgroup
+ * fits one dimension in one slot of the workspace, and a call keeps as many dimensions in flight
+ * as the workspace has slots for, the widest dimensions first; there is no other limit.  A slot
+ * is mivq_codebook1d_workspace_bytes(n, w, method, 1) bytes, w the widest of the dimensions in
+ * flight (EXACT keeps (2^w - 1)(n + 1) int32 of argmins per slot), so the same bytes hold more
+ * of the narrower dimensions that follow.  The result does not depend on the workspace size.
+ * The first centre of a dimension takes one draw, or more where a draw is rejected (probability
+ * n / 2^64 each), every further centre one; a dimension that runs out of draws reuses the last
+ * one and rejects no more, so pass spare draws beyond 2^max width to keep the generator's
+ * sequence.
+ * A row that is not ascending or holds non-finite values gives unspecified levels but no access
+ * outside the row, its slot and its levels.
+ * n < 0, d < 0, an unknown method, a width outside 0..8, an lv_off that does not match the widths,
+ * a null pointer or fewer than 2^max width draws return MIVQ_ERR_INVALID, a workspace below one
+ * slot of the widest dimension MIVQ_ERR_WORKSPACE and n above 2^26 MIVQ_ERR_UNSUPPORTED, all
+ * before any launch; n == 0 or d == 0 returns MIVQ_OK without one.  The size query returns 0 for
+ * arguments fit would refuse. */
+#define MIVQ_CB1D_EXACT 0
+#define MIVQ_CB1D_LLOYD 1
+size_t mivq_codebook1d_workspace_bytes(int64_t n, int32_t max_width, int32_t method,
+                                       int32_t dims_at_once);
+int mivq_codebook1d_fit(const float* cols, int64_t n, int32_t d, const int32_t* width,
+                        const int32_t* lv_off, int32_t method, const uint64_t* draws, int32_t ndraws,
+                        void* workspace, size_t workspace_bytes, float* levels, double* sse,
+                        void* stream);
+
 /* ------------------------------------------------------ ADC search
  * Flat asymmetric-distance search over PQ codes; the GPU counterpart of
  * FlatQuantizedIndex.search_with_scores (methods/search/flat_quantized_index.py:45-76),

@@ -20,6 +20,7 @@ import threading
 from pathlib import Path
 from typing import NamedTuple, Optional, Tuple
 
+import numpy as np
 import torch  # noqa: F401  (must be imported before libmivq: they share libamdhip64.so.7)
 
 _PKG_ROOT = Path(__file__).resolve().parent.parent  # vector-quantization_amd/
@@ -87,6 +88,8 @@ SIGNATURES = {
     "mivq_rankaware_flat_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
     "mivq_rankaware_flat_search": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64,
                                               _vp, _sz, _vp, _vp, _vp]),
+    "mivq_codebook1d_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "mivq_codebook1d_fit": (_c.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _sz, _vp, _vp, _vp]),
     "mivq_adc_lut": (_c.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
     "mivq_adc_search_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
     "mivq_adc_search": (_c.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _sz, _vp, _vp, _c.c_uint32,
@@ -953,6 +956,97 @@ def rankaware_flat_search(qy: torch.Tensor, codes: torch.Tensor, st: RankAwareSt
     _call("mivq_rankaware_flat_search", _ptr(qy), nq, _ptr(codes), n, d, _ptr(lv32), _ptr(st.lv_off), _ptr(st.pos),
           _ptr(st.width), st.code_size, metric, k, id_offset, _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids), _stream())
     return dists, ids
+
+
+# ----------------------------------------------------------------- fitted 1-D codebooks
+CB1D_EXACT = 0
+CB1D_LLOYD = 1
+CB1D_METHODS = {"exact": CB1D_EXACT, "lloyd": CB1D_LLOYD}
+CB1D_WORKSPACE_BUDGET = 8 << 30   # bytes of workspace one codebook1d_fit call may ask for
+CB1D_DRAWS = 320                  # 2^8 seeds plus room for rejected index draws
+
+
+def mt19937_64(seed: int, count: int) -> list:
+    """The first `count` raw outputs of the 64-bit Mersenne Twister seeded like std::mt19937_64."""
+    m64 = (1 << 64) - 1
+    mt = [seed & m64]
+    for i in range(1, 312):
+        mt.append((6364136223846793005 * (mt[-1] ^ (mt[-1] >> 62)) + i) & m64)
+    out = []
+    while len(out) < count:
+        for i in range(312):
+            x = (mt[i] & 0xFFFFFFFF80000000) | (mt[(i + 1) % 312] & 0x7FFFFFFF)
+            mt[i] = mt[(i + 156) % 312] ^ (x >> 1) ^ (0xB5026F5AA96619E9 if x & 1 else 0)
+        for x in mt:
+            x ^= (x >> 29) & 0x5555555555555555
+            x ^= (x << 17) & 0x71D67FFFEDA60000
+            x ^= (x << 37) & 0xFFF7EEE000000000
+            out.append((x ^ (x >> 43)) & m64)
+    return out[:count]
+
+
+def codebook1d_tables(width) -> Tuple[np.ndarray, np.ndarray]:
+    """(width int32 (d,), lv_off int32 (d + 1,)) of per-dimension tables of 2 ** width levels."""
+    width = np.ascontiguousarray(np.asarray(width).reshape(-1), dtype=np.int32)
+    if width.size and (width.min() < 0 or width.max() > 8):
+        raise ValueError("codebook1d: widths must be in [0, 8]")
+    lv_off = np.concatenate(([0], np.cumsum(np.int64(1) << width.astype(np.int64))))
+    if lv_off[-1] >= 2 ** 31:
+        raise ValueError("codebook1d: level tables too large")
+    return width, np.ascontiguousarray(lv_off, dtype=np.int32)
+
+
+def codebook1d_workspace(n: int, width, method: str, device: Optional[torch.device] = None) -> Tuple[int, int]:
+    """(bytes, slots) of the workspace codebook1d_fit allocates by default: slots of the widest
+    dimension (mivq_codebook1d_workspace_bytes), one per dimension of non-zero width, as many as
+    fit into CB1D_WORKSPACE_BUDGET and into half of the device memory that is free now, at least
+    one.  Narrower dimensions, fitted later in the call, get more slots out of the same bytes."""
+    width, _ = codebook1d_tables(width)
+    live = int(np.count_nonzero(width))
+    if method not in CB1D_METHODS:
+        raise ValueError(f"codebook1d: method must be 'exact' or 'lloyd', got {method!r}")
+    slot = load_library().mivq_codebook1d_workspace_bytes(n, int(width.max()) if live else 0, CB1D_METHODS[method], 1)
+    if slot == 0:
+        raise ValueError(f"codebook1d: n={n} is not supported")
+    budget = CB1D_WORKSPACE_BUDGET
+    if device is not None and torch.cuda.is_available():
+        budget = min(budget, torch.cuda.mem_get_info(device)[0] // 2)
+    slots = max(1, min(max(live, 1), budget // slot))
+    return slot * slots, slots
+
+
+def codebook1d_fit(cols_sorted: torch.Tensor, width, method: str, seed: int = 0,
+                   workspace_bytes: Optional[int] = None) -> Tuple[torch.Tensor, np.ndarray, torch.Tensor]:
+    """Fit 2 ** width[j] levels to every row of cols_sorted ((d, n) f32, each row ascending) with
+    mivq_codebook1d_fit: method "exact" (optimal 1-D k-means) or "lloyd" (k-means++ from
+    mt19937_64(seed), <= 50 passes).  Returns (levels f32 (lv_off[d],) on the device, lv_off
+    int32 (d + 1,) on the host, sse f64 (d,) on the device); a width-0 dimension keeps level 0
+    and sse 0.  The workspace is codebook1d_workspace's (or `workspace_bytes`, at least one slot);
+    its size changes how many dimensions run at once, never the result."""
+    if method not in CB1D_METHODS:
+        raise ValueError(f"codebook1d: method must be 'exact' or 'lloyd', got {method!r}")
+    _check(cols_sorted, "cols_sorted", torch.float32, 2)
+    d, n = cols_sorted.shape
+    width, lv_off = codebook1d_tables(width)
+    if width.shape[0] != d:
+        raise ValueError(f"codebook1d: {width.shape[0]} widths for {d} rows")
+    dev = cols_sorted.device
+    levels = torch.zeros(int(lv_off[-1]), dtype=torch.float32, device=dev)
+    sse = torch.zeros(d, dtype=torch.float64, device=dev)
+    live = int(np.count_nonzero(width))
+    if n == 0 or live == 0:
+        return levels, lv_off, sse
+    m = CB1D_METHODS[method]
+    if workspace_bytes is None:
+        workspace_bytes = codebook1d_workspace(n, width, method, dev)[0]
+    ws = workspace(workspace_bytes, dev)
+    draws = None
+    if m == CB1D_LLOYD:
+        draws = torch.from_numpy(np.array(mt19937_64(seed, CB1D_DRAWS), dtype=np.uint64).view(np.int64)).to(dev)
+    _call("mivq_codebook1d_fit", _ptr(cols_sorted), n, d, width.ctypes.data_as(_vp), lv_off.ctypes.data_as(_vp), m,
+          _ptr(draws), CB1D_DRAWS if draws is not None else 0, _ptr(ws), int(workspace_bytes), _ptr(levels), _ptr(sse),
+          _stream())
+    return levels, lv_off, sse
 
 
 # ----------------------------------------------------------------- ADC / flat search

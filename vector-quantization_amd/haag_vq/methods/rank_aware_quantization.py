@@ -23,8 +23,17 @@ Parity: the GEMM's summation order differs from numpy's, so an index can differ 
 reference's only by one and only where the rotated value lies within rounding distance of the
 boundary between two levels; decoded rows agree to an f32 ulp.
 
-The data-fitted codebooks (``codebook="lloyd"`` / ``"exact"``) come from the SAQ engine, which is
-out of scope of this build: the constructor accepts them, ``fit`` raises.
+The data-fitted codebooks (``codebook="lloyd"`` / ``"exact"``): the reference fits them with the
+SAQ engine, which is out of scope of this build, so with the default ``codebook_engine="saq"``
+the constructor accepts them and ``fit`` raises.  ``codebook_engine="device"`` fits them here:
+``fit`` takes the reference's sample (all rows, or 200 000 drawn by ``default_rng(0)``), centres
+and rotates it on the device, rounds to f32, sorts every column (``torch.sort``) and hands the
+(D, n) columns to ``mivq_codebook1d_fit``: the globally optimal 1-D k-means by dynamic
+programming (``"exact"``) or k-means++ / Lloyd (``"lloyd"``, the study's own method), one
+workgroup per dimension, bit for bit the reference builders' sequential fp64 arithmetic on the
+same columns.  A dimension with no more than ``2 ** bits`` distinct sample values gets those
+values, padded with the last one to ``2 ** bits`` levels (the reference leaves its Lloyd table
+short there); a row beyond the last level then carries another index of the same value.
 """
 
 from __future__ import annotations
@@ -37,6 +46,7 @@ from .base_quantizer import BaseQuantizer
 from .ffd_packing import ffd_layout
 
 _LLOYD_CACHE: dict = {}
+CB_SAMPLE = 200_000   # rows the data-fitted codebooks are trained on (the reference's CB_SAMPLE)
 
 
 def _lloyd_1d_normal(num_levels: int, seed: int, n_samples: int = 200_000, max_iter: int = 100,
@@ -97,14 +107,17 @@ def allocate_bits(var: np.ndarray, Dg: np.ndarray, avg_bits: float, alpha: float
 
 class RankAwareQuantizer(BaseQuantizer):
     def __init__(self, avg_bits: float, alpha: float = 1.0, max_bits: int = 8, seed: int = 0,
-                 packing: str = "dense", codebook: str = "gaussian"):
+                 packing: str = "dense", codebook: str = "gaussian", codebook_engine: str = "saq"):
         if max_bits < 1 or max_bits > 8:
             raise ValueError("max_bits must be in [1, 8]")
         if packing not in ("dense", "ffd"):
             raise ValueError("packing must be 'dense' or 'ffd'")
         if codebook not in ("gaussian", "lloyd", "exact"):
             raise ValueError("codebook must be 'gaussian', 'lloyd', or 'exact'")
+        if codebook_engine not in ("saq", "device"):
+            raise ValueError("codebook_engine must be 'saq' or 'device'")
         self.codebook = codebook
+        self.codebook_engine = codebook_engine
         self.avg_bits = float(avg_bits)
         self.alpha = float(alpha)
         self.max_bits = int(max_bits)
@@ -148,7 +161,7 @@ class RankAwareQuantizer(BaseQuantizer):
         return int(N), _arrays.to_host(S), _arrays.to_host(G)
 
     def fit(self, X) -> None:
-        if self.codebook != "gaussian":
+        if self.codebook != "gaussian" and self.codebook_engine == "saq":
             raise ValueError(f"codebook={self.codebook!r} is fitted by the SAQ engine, which is out of scope of the "
                              "MI355X build; use codebook='gaussian'")
         if not _arrays.is_tensor(X):
@@ -172,9 +185,51 @@ class RankAwareQuantizer(BaseQuantizer):
         Dg[0] = 1.0
         self._Dg = Dg
         self.bits = allocate_bits(self.var, Dg, self.avg_bits, self.alpha, self.max_bits)
-        scale = np.sqrt(self.var)
-        self.cb = [self._levels[int(b)] * scale[d] for d, b in enumerate(self.bits)]
+        if self.codebook == "gaussian":
+            scale = np.sqrt(self.var)
+            self.cb = [self._levels[int(b)] * scale[d] for d, b in enumerate(self.bits)]
+        else:
+            self.cb = self._fit_codebooks(X)
         self._layout()
+
+    def _sample_projection(self, X) -> torch.Tensor:
+        """The sample the fitted codebooks are trained on, rotated: (D, n) f32 on the device, all
+        rows of X or CB_SAMPLE of them drawn by ``default_rng(0)``; ``(x - mu) V`` in fp64 on the
+        device, rounded to f32."""
+        N = int(X.shape[0])
+        if N > CB_SAMPLE:
+            idx = np.random.default_rng(0).choice(N, CB_SAMPLE, replace=False)
+            X = X[torch.from_numpy(idx).to(X.device)] if _arrays.is_tensor(X) else np.asarray(X)[idx]
+        n = int(X.shape[0])
+        dev = _arrays.device()
+        mu = _arrays.to_device(np.ascontiguousarray(self.mu, dtype=np.float64), torch.float64)
+        V = _arrays.to_device(np.ascontiguousarray(self.V, dtype=np.float64), torch.float64)
+        cols = torch.empty((self.D, n), dtype=torch.float32, device=dev)
+        for s, e in _arrays.row_chunks(n, self.D * 24, self._stage_bytes):
+            x = X[s:e]
+            if _arrays.is_tensor(x):
+                dt = x.dtype if x.dtype in (torch.float32, torch.float64) else torch.float64
+            else:
+                dt = torch.float32 if x.dtype == np.float32 else torch.float64
+            y = _native.gemm_f64(_native.rankaware_center(_arrays.to_device(x, dt).contiguous(), mu), V, False)
+            cols[:, s:e] = y.to(torch.float32).T
+        return cols
+
+    def sample_columns(self, X) -> torch.Tensor:
+        """What ``_fit_codebooks`` hands to ``mivq_codebook1d_fit``: row d = the sample's rotated
+        dimension d (``_sample_projection``) in ascending order."""
+        return torch.sort(self._sample_projection(X), dim=1).values.contiguous()
+
+    def _fit_codebooks(self, X) -> list:
+        """The reference's step 5 for ``codebook`` "lloyd" / "exact" on the fitted ``mu``, ``V``
+        and ``bits``: one table of ``2 ** bits[d]`` f64 levels per dimension ([0.0] for 0 bits)."""
+        if self.codebook not in _native.CB1D_METHODS:
+            raise ValueError(f"codebook={self.codebook!r} has no fitted tables")
+        if not _arrays.is_tensor(X):
+            X = np.asarray(X)
+        levels, lv_off, _ = _native.codebook1d_fit(self.sample_columns(X), self.bits, self.codebook)
+        lv = _arrays.to_host(levels).astype(np.float64)
+        return [lv[lv_off[d]:lv_off[d + 1]] if b else np.array([0.0]) for d, b in enumerate(self.bits)]
 
     def _layout(self) -> None:
         """Bit offsets, the FFD layout and the code size, from ``bits`` and ``packing``."""

@@ -145,12 +145,18 @@ def quantizer_state(q: BaseQuantizer) -> dict:
     if isinstance(q, RankAwareQuantizer):
         if q.V is None:
             raise ValueError("save(): the RankAwareQuantizer is not fitted")
-        return dict(qtype=np.array("rankaware"), avg_bits=np.array(q.avg_bits), alpha=np.array(q.alpha),
-                    max_bits=np.array(q.max_bits), seed=np.array(q.seed), packing=np.array(q.packing),
-                    mu=np.asarray(q.mu, dtype=np.float64), V=np.ascontiguousarray(q.V, dtype=np.float64),
-                    var=np.asarray(q.var, dtype=np.float64), bits=np.asarray(q.bits, dtype=np.int64),
-                    cb=np.concatenate(q.cb).astype(np.float64), levels=np.concatenate(q._levels).astype(np.float64),
-                    Dg=np.asarray(q._Dg, dtype=np.float64))
+        st = dict(qtype=np.array("rankaware"), avg_bits=np.array(q.avg_bits), alpha=np.array(q.alpha),
+                  max_bits=np.array(q.max_bits), seed=np.array(q.seed), packing=np.array(q.packing),
+                  mu=np.asarray(q.mu, dtype=np.float64), V=np.ascontiguousarray(q.V, dtype=np.float64),
+                  var=np.asarray(q.var, dtype=np.float64), bits=np.asarray(q.bits, dtype=np.int64),
+                  cb=np.concatenate(q.cb).astype(np.float64), levels=np.concatenate(q._levels).astype(np.float64),
+                  Dg=np.asarray(q._Dg, dtype=np.float64))
+        # written only when not the defaults: a gaussian quantizer's file keeps its bytes
+        if q.codebook != "gaussian":
+            st["codebook"] = np.array(q.codebook)
+        if q.codebook_engine != "saq":
+            st["codebook_engine"] = np.array(q.codebook_engine)
+        return st
     if isinstance(q, ExtendedRaBitQuantizer):
         if q.P is None:
             raise ValueError("save(): the ExtendedRaBitQuantizer is not fitted")
@@ -186,7 +192,9 @@ def quantizer_from_state(z) -> BaseQuantizer:
         q.mu = np.array(z["mu"])
     elif qt == "rankaware":
         q = RankAwareQuantizer(avg_bits=float(z["avg_bits"]), alpha=float(z["alpha"]), max_bits=int(z["max_bits"]),
-                               seed=int(z["seed"]), packing=str(z["packing"]))
+                               seed=int(z["seed"]), packing=str(z["packing"]),
+                               codebook=str(z["codebook"]) if "codebook" in z else "gaussian",
+                               codebook_engine=str(z["codebook_engine"]) if "codebook_engine" in z else "saq")
         q.mu, q.V, q.var = np.array(z["mu"]), np.array(z["V"]), np.array(z["var"])
         q.bits = np.array(z["bits"], dtype=np.int64)
         q.D = int(q.bits.shape[0])
