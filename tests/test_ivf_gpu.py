@@ -297,6 +297,10 @@ def test_save_load(ivf_idx, tmp_path):
     ivf_idx.fit(make_data())
     p = tmp_path / "ivfpq.npz"
     ivf_idx.save(str(p))
+    with np.load(p, allow_pickle=False) as z:  # the file format (an L2 index: tau is there)
+        assert sorted(z.files) == sorted(["meta", "coarse", "pq", "offsets", "codes", "ids", "tau"])
+        assert z["meta"].dtype == np.int64 and z["meta"].shape == (7,)
+        assert z["codes"].dtype == np.uint8 and z["ids"].dtype == np.int32
     loaded = FaissIvfPqIndex(K=8, m=4, nbits=4, nprobe=4)
     loaded.load(str(p))
     Q = make_data(N=5, seed=1)

@@ -322,6 +322,10 @@ def test_index_against_train_pq_its_engine_and_numpy(dev, metric, tmp_path):
     # save / load into a fresh index
     path = tmp_path / "listpq.npz"
     idx.save(path)
+    with np.load(path, allow_pickle=False) as z:  # the file format
+        assert sorted(z.files) == sorted(["coarse", "codebooks", "offsets", "codes", "ids", "M", "B", "niter", "seed", "K",
+                                          "nprobe", "metric", "N", "D"])
+        assert z["codes"].dtype == np.uint8 and z["codes"].shape == (1500, 4) and z["ids"].dtype == np.int32
     other = IvfListPqIndex(_factory(M=2, B=4), K=3, nprobe=9)
     other.load(path)
     assert (other._M, other._B, other._K, other.nprobe, other.ntotal) == (4, 8, 4, 4, 1500)

@@ -374,6 +374,12 @@ def test_index_against_its_engine_and_the_flat_search(dev, kind, bits, metric, t
     # save / load
     path = tmp_path / "ivfq.npz"
     idx.save(path)
+    with np.load(path, allow_pickle=False) as z:  # the file format
+        assert sorted(z.files) == sorted(["coarse", "offsets", "codes", "ids", "kind", "bits", "K", "nprobe", "metric", "N",
+                                          "D", "param0"] + (["param1"] if kind == "sq" else []))
+        # (16-bit SQ rows are written as the int16 they are held in)
+        assert z["codes"].dtype == (np.int16 if np.dtype(dt).itemsize == 2 else np.uint8)
+        assert z["codes"].shape == (1500, width) and z["ids"].dtype == np.int32
     other = IvfQuantizedIndex(_factory("lvq", 1), K=3, nprobe=2)
     other.load(path)
     assert (other._kind, other._bits, other._K, other.nprobe, other.ntotal) == (kind, bits, 8, 8, 1500)

@@ -379,6 +379,8 @@ def test_index_save_load_roundtrip(tmp_path, dev, metric):
     idx.save(p)
     with np.load(p, allow_pickle=False) as z:
         assert all(z[f].dtype.kind in "iufU" for f in z.files)
+        assert sorted(z.files) == sorted(["coarse", "offsets", "codes", "ids", "nlist", "nprobe", "qb", "metric", "D"])
+        assert z["codes"].dtype == np.uint8 and z["ids"].dtype == np.int32
     fresh = RaBitQIVFIndex()
     fresh.load(p)
     assert (fresh._qb, fresh._nprobe, fresh._nlist, fresh._metric, fresh._D) == (8, 5, 16, metric, 32)

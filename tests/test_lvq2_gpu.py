@@ -418,6 +418,10 @@ def test_index_file_round_trip(dev, tmp_path):
     ix.fit(c["X"], "ip")
     path = tmp_path / "ix" / "lvq2.npz"
     ix.save(path)
+    with np.load(path, allow_pickle=False) as z:  # the file format
+        assert sorted(z.files) == sorted(["codes1", "codes2", "mu", "primary_bits", "residual_bits", "metric",
+                                          "refine_factor", "N", "D"])
+        assert z["codes1"].dtype == np.uint8 and z["codes2"].dtype == np.uint8
     back = LVQ2Index(4, 4, refine_factor=9)
     back.load(path)
     assert back.refine_factor == 4 and back.ntotal == 1500 and back.memory_footprint() == ix.memory_footprint()

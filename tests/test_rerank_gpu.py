@@ -299,6 +299,9 @@ def test_refined_index_file_round_trip(refined, tmp_path):
     path = tmp_path / "ix" / "refined.npz"
     refined["ix"].save(path)
     assert path.exists() and (tmp_path / "ix" / "refined.npz.base").exists()
+    with np.load(path, allow_pickle=False) as z:  # the file format: an f32 store has no param* entries
+        assert sorted(z.files) == sorted(["store", "kind", "bits", "metric", "refine_factor", "N", "D"])
+        assert z["store"].dtype == np.float32 and z["store"].shape == (c["N"], c["D"])
     back = RefinedIndex(FlatADCIndex(ProductQuantizer(M=c["M"], B=8)), None, refine_factor=3)
     back.load(path)
     assert back.refine_factor == c["factor"] and back.ntotal == c["N"]

@@ -1,4 +1,5 @@
-// adc_internal.h — what adc.hip, adc_filtered.hip and exact_search.hip share.
+// adc_internal.h — what adc.hip, adc_filtered.hip and exact_search.hip share; the query-block
+// dispatch serves the searches over probed lists too (ivf_code.hip, ivf_listpq.hip).
 #pragma once
 
 #include "mivq_common.h"
@@ -12,11 +13,14 @@ constexpr int kScanWaves = 16;  // waves per scan workgroup (adc and flat)
 // Row chunks per query block of a scan with QB queries per workgroup (adc.hip).
 int64_t adc_chunks(int64_t nq, int64_t n, int QB);
 
-// Host side: f(std::integral_constant<int, QB>) for the queries per scan workgroup, 8, 4, 2 or 1.
-template <typename F>
+// Host side: f(std::integral_constant<int, QB>) for the queries per scan workgroup, 8, 4, 2 or 1
+// (MAX_QB = 4: a caller whose blocks are never wider, so that it has no kernel for 8).
+template <int MAX_QB = 8, typename F>
 auto with_query_block(int QB, F&& f) {
+    if constexpr (MAX_QB >= 8) {
+        if (QB == 8) return f(std::integral_constant<int, 8>{});
+    }
     switch (QB) {
-        case 8: return f(std::integral_constant<int, 8>{});
         case 4: return f(std::integral_constant<int, 4>{});
         case 2: return f(std::integral_constant<int, 2>{});
         default: return f(std::integral_constant<int, 1>{});

@@ -2,12 +2,16 @@
 // (exact_search.hip over a flat database, ivf_code.hip over probed lists), the scan of one code
 // row against the queries in LDS, and the SQ / LVQ encode and decode kernels, which sq.hip and
 // lvq.hip launch with one parameter row for the database and ivf_code.hip with the parameter
-// rows and the centroid of each row's list (PER_ROW, the pattern of rabitq_internal.h).
+// rows and the centroid of each row's list (PER_ROW, the pattern of rabitq_internal.h).  Host side:
+// the dispatch from a run-time code width to a format (with_sq_bits / with_lvq_bits /
+// with_erq_bits), the load modes of a code array, and the G and store width of an LVQ encode.
 #pragma once
 
 #include "mivq_common.h"
 
 #include <float.h>
+
+#include <type_traits>
 
 namespace mivq {
 
@@ -149,6 +153,57 @@ struct Fmt {
         return make_float2(__fmul_rn(__fmul_rn(__fmul_rn(0.5f, __uint_as_float(u1)), 2.0f), inv_d_sqrt), 0.0f);
     }
 };
+
+// ---------------------------------------------------------------- host side: format dispatch
+// f(std::integral_constant<int, FMT>) for the format of a code width the caller has checked, so
+// that an entry point names its template once (the pattern of with_topk_regs): LVQ and Extended
+// RaBitQ at nbits = 1 .. 8, SQ at 4 / 8 / 16.
+template <int BASE, typename F>
+auto with_stream_bits(int nbits, F&& f) {
+    switch (nbits) {
+        case 1: return f(std::integral_constant<int, BASE + 0>{});
+        case 2: return f(std::integral_constant<int, BASE + 1>{});
+        case 3: return f(std::integral_constant<int, BASE + 2>{});
+        case 4: return f(std::integral_constant<int, BASE + 3>{});
+        case 5: return f(std::integral_constant<int, BASE + 4>{});
+        case 6: return f(std::integral_constant<int, BASE + 5>{});
+        case 7: return f(std::integral_constant<int, BASE + 6>{});
+        default: return f(std::integral_constant<int, BASE + 7>{});
+    }
+}
+template <typename F>
+auto with_lvq_bits(int nbits, F&& f) { return with_stream_bits<kLvq>(nbits, f); }
+template <typename F>
+auto with_erq_bits(int nbits, F&& f) { return with_stream_bits<kErq>(nbits, f); }
+template <typename F>
+auto with_sq_bits(int nbits, F&& f) {
+    switch (nbits) {
+        case 4: return f(std::integral_constant<int, kSq4>{});
+        case 8: return f(std::integral_constant<int, kSq8>{});
+        default: return f(std::integral_constant<int, kSq16>{});
+    }
+}
+
+// SQ-16 codes are read and written as uint16: MIVQ_OK, or the error of `name`.
+inline int sq16_aligned(const char* name, int nbits, const void* codes) {
+    MIVQ_REQUIRE(nbits != 16 || reinterpret_cast<uintptr_t>(codes) % 2 == 0, MIVQ_ERR_INVALID,
+                 "%s: 16-bit codes must be 2-byte aligned", name);
+    return MIVQ_OK;
+}
+
+// How scan_row may load the rows of an array: `wide` when every row start is aligned for loads
+// of wide_bytes, `narrow` for 4-byte loads.
+struct LoadModes {
+    int wide, narrow;
+};
+inline LoadModes load_modes(const void* base, int64_t row_bytes, int wide_bytes) {
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(base);
+    return {addr % wide_bytes == 0 && row_bytes % wide_bytes == 0, addr % 4 == 0 && row_bytes % 4 == 0};
+}
+template <int FMT>
+LoadModes code_load_modes(const void* base, int d) {
+    return load_modes(base, Fmt<FMT>::row_bytes(d), Fmt<FMT>::kWideWords * 4);
+}
 
 // ---------------------------------------------------------------- one row against QB queries
 // Where a workgroup's LDS rows are: [QB][dp] queries at qv, the parameter rows pa (SQ den /
@@ -370,6 +425,30 @@ __global__ void sq_decode_kernel(const void* __restrict__ codes, int64_t n, int 
 
 // ---------------------------------------------------------------- LVQ encode / decode
 constexpr int kLvqMaxRegGroups = 6;  // groups of 8 dims a lane keeps in registers: d <= 3072
+
+// Host side: f(std::integral_constant<int, G>) for the G of an LVQ encode kernel whose lanes hold
+// per_lane groups each: per_lane itself up to 4 (MIN_G at the least: a smaller row leaves the
+// other groups predicated off), kLvqMaxRegGroups up to that, 0 (the row read twice) beyond.
+template <int MIN_G = 1, typename F>
+void with_lvq_groups(int per_lane, F&& f) {
+    if constexpr (MIN_G <= 1) {
+        if (per_lane <= 1) return f(std::integral_constant<int, 1>{});
+    }
+    if (per_lane <= 2) return f(std::integral_constant<int, 2>{});
+    if (per_lane == 3) return f(std::integral_constant<int, 3>{});
+    if (per_lane == 4) return f(std::integral_constant<int, 4>{});
+    if (per_lane <= kLvqMaxRegGroups) return f(std::integral_constant<int, kLvqMaxRegGroups>{});
+    return f(std::integral_constant<int, 0>{});
+}
+
+// The widest store (8, 4, 2 or 1 bytes) every group start of every row of an array of B-bit
+// codes is aligned for (lvq_emit's `sw`).
+inline int lvq_store_width(const void* base, int64_t row_bytes, int B) {
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(base);
+    int sw = 8;
+    while (sw > 1 && (B % sw != 0 || row_bytes % sw != 0 || addr % sw != 0)) sw >>= 1;
+    return sw;
+}
 
 // rint((r - lo) / delta) needs the correctly rounded quotient only where it can land on or next
 // to a tie.  With rcp = RN(1 / delta): q0 = RN(a rcp), the exact residual e = a - delta q0 (one

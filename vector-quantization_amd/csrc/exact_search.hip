@@ -130,13 +130,9 @@ hipError_t launch_scan(const float* q, int64_t nq, const uint8_t* codes, int64_t
     auto kern = code_scan_kernel<FMT, R, QB>;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return e;
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(codes);
-    const int rb = F::row_bytes(d);
-    const int wb = F::kWideWords * 4;
-    const int wide = addr % wb == 0 && rb % wb == 0;
-    const int narrow = addr % 4 == 0 && rb % 4 == 0;
+    const LoadModes lm = code_load_modes<FMT>(codes, d);
     hipLaunchKernelGGL(kern, dim3((unsigned)nch, (unsigned)ceil_div(nq, QB)), dim3(kScanWaves * 64), smem, st, q, nq, codes,
-                       n, d, ga, gb, metric, k, id_offset, ceil_div(n, nch), wide, narrow, pd, pi);
+                       n, d, ga, gb, metric, k, id_offset, ceil_div(n, nch), lm.wide, lm.narrow, pd, pi);
     return hipGetLastError();
 }
 
@@ -426,17 +422,11 @@ extern "C" int mivq_sq_flat_search(const float* q, int64_t nq, const void* codes
     const int rc = search_prologue("sq_flat_search", nq, n, d, Fmt<kSq8>::kPolicy, metric, k, id_offset, dists, ids, st, &done);
     if (rc != MIVQ_OK || done) return rc;
     MIVQ_REQUIRE(q && codes && lo && den, MIVQ_ERR_INVALID, "sq_flat_search: null pointer");
-    MIVQ_REQUIRE(nbits != 16 || reinterpret_cast<uintptr_t>(codes) % 2 == 0, MIVQ_ERR_INVALID,
-                 "sq_flat_search: 16-bit codes must be 2-byte aligned");
-    const uint8_t* c = static_cast<const uint8_t*>(codes);
-    if (nbits == 4)
-        return exact_flat_search<kSq4>("sq_flat_search", q, nq, c, n, d, den, lo, metric, k, id_offset, workspace,
-                                      workspace_bytes, dists, ids, st);
-    if (nbits == 8)
-        return exact_flat_search<kSq8>("sq_flat_search", q, nq, c, n, d, den, lo, metric, k, id_offset, workspace,
-                                      workspace_bytes, dists, ids, st);
-    return exact_flat_search<kSq16>("sq_flat_search", q, nq, c, n, d, den, lo, metric, k, id_offset, workspace,
-                                   workspace_bytes, dists, ids, st);
+    if (const int ra = sq16_aligned("sq_flat_search", nbits, codes)) return ra;
+    return with_sq_bits(nbits, [&](auto F) {
+        return exact_flat_search<decltype(F)::value>("sq_flat_search", q, nq, static_cast<const uint8_t*>(codes), n, d, den,
+                                                     lo, metric, k, id_offset, workspace, workspace_bytes, dists, ids, st);
+    });
 }
 
 extern "C" int mivq_rabitq_flat_search(const float* q, int64_t nq, const uint8_t* codes, int64_t n, int32_t d,
@@ -462,22 +452,10 @@ extern "C" int mivq_lvq_flat_search(const float* q, int64_t nq, const uint8_t* c
     const int rc = search_prologue("lvq_flat_search", nq, n, d, Fmt<kLvq>::kPolicy, metric, k, id_offset, dists, ids, st, &done);
     if (rc != MIVQ_OK || done) return rc;
     MIVQ_REQUIRE(q && codes && mu, MIVQ_ERR_INVALID, "lvq_flat_search: null pointer");
-#define MIVQ_LVQ_SEARCH(B)                                                                                             \
-    case B:                                                                                                            \
-        return exact_flat_search<kLvq + B - 1>("lvq_flat_search", q, nq, codes, n, d, mu, nullptr, metric, k, id_offset, \
-                                              workspace, workspace_bytes, dists, ids, st)
-    switch (nbits) {
-        MIVQ_LVQ_SEARCH(1);
-        MIVQ_LVQ_SEARCH(2);
-        MIVQ_LVQ_SEARCH(3);
-        MIVQ_LVQ_SEARCH(4);
-        MIVQ_LVQ_SEARCH(5);
-        MIVQ_LVQ_SEARCH(6);
-        MIVQ_LVQ_SEARCH(7);
-        MIVQ_LVQ_SEARCH(8);
-        default: return MIVQ_ERR_INVALID;
-    }
-#undef MIVQ_LVQ_SEARCH
+    return with_lvq_bits(nbits, [&](auto F) {
+        return exact_flat_search<decltype(F)::value>("lvq_flat_search", q, nq, codes, n, d, mu, nullptr, metric, k, id_offset,
+                                                     workspace, workspace_bytes, dists, ids, st);
+    });
 }
 
 extern "C" size_t mivq_extrabitq_flat_search_workspace_bytes(int64_t nq, int64_t n, int32_t d, int32_t k) {
@@ -498,20 +476,8 @@ extern "C" int mivq_extrabitq_flat_search(const float* qy, int64_t nq, const uin
     if (rc != MIVQ_OK || done) return rc;
     MIVQ_REQUIRE(qy && codes && levels, MIVQ_ERR_INVALID, "extrabitq_flat_search: null pointer");
     const float* lv = reinterpret_cast<const float*>(levels);
-#define MIVQ_ERQ_SEARCH(B)                                                                                             \
-    case B:                                                                                                            \
-        return exact_flat_search<kErq + B - 1>("extrabitq_flat_search", qy, nq, codes, n, d, lv, nullptr, metric, k,   \
-                                              id_offset, workspace, workspace_bytes, dists, ids, st)
-    switch (nbits) {
-        MIVQ_ERQ_SEARCH(1);
-        MIVQ_ERQ_SEARCH(2);
-        MIVQ_ERQ_SEARCH(3);
-        MIVQ_ERQ_SEARCH(4);
-        MIVQ_ERQ_SEARCH(5);
-        MIVQ_ERQ_SEARCH(6);
-        MIVQ_ERQ_SEARCH(7);
-        MIVQ_ERQ_SEARCH(8);
-        default: return MIVQ_ERR_INVALID;
-    }
-#undef MIVQ_ERQ_SEARCH
+    return with_erq_bits(nbits, [&](auto F) {
+        return exact_flat_search<decltype(F)::value>("extrabitq_flat_search", qy, nq, codes, n, d, lv, nullptr, metric, k,
+                                                     id_offset, workspace, workspace_bytes, dists, ids, st);
+    });
 }

@@ -12,7 +12,7 @@
 //   ivf_sq_fit_kernel     one workgroup per list: min / max of the residuals in every dimension.
 //   sq_/lvq_encode_kernel, sq_/lvq_decode_kernel <PER_ROW>: the flat kernels (code_internal.h)
 //                         with the parameters and the centroid of row i taken at assign[i].
-//   ivf_code_prep_kernel  the driver's pair prologue, nothing else.
+//   ivf_prep_kernel       (ivf_internal.h) the driver's pair prologue, nothing else.
 //   ivf_code_scan_kernel  the QB query rows and the list's parameter rows and centroid in LDS,
 //                         lane = row, the row read once by scan_row (code_internal.h: the loads
 //                         and chains of code_scan_kernel), WaveTopK selection inside the scan, the
@@ -82,34 +82,20 @@ __global__ __launch_bounds__(256) void ivf_sq_fit_kernel(const float* __restrict
     }
 }
 
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 template <bool VEC>
 void launch_ivf_lvq_encode(const float* x, int64_t n, int d, const float* coarse, const uint32_t* assign,
                            const float* mu, int B, int sw, uint8_t* codes, hipStream_t st) {
     const int per_lane = (int)ceil_div((d + 7) / 8, 64);
     const dim3 grid((unsigned)std::min<int64_t>(ceil_div(n, 4), (int64_t)device_cus() * 32));
-#define MIVQ_IVF_LVQ_ENC(G) \
-    hipLaunchKernelGGL((lvq_encode_kernel<G, VEC, true>), grid, dim3(256), 0, st, x, n, d, coarse, assign, mu, B, sw, codes)
-    if (per_lane <= 1) MIVQ_IVF_LVQ_ENC(1);
-    else if (per_lane == 2) MIVQ_IVF_LVQ_ENC(2);
-    else if (per_lane == 3) MIVQ_IVF_LVQ_ENC(3);
-    else if (per_lane == 4) MIVQ_IVF_LVQ_ENC(4);
-    else if (per_lane <= kLvqMaxRegGroups) MIVQ_IVF_LVQ_ENC(kLvqMaxRegGroups);
-    else MIVQ_IVF_LVQ_ENC(0);
-#undef MIVQ_IVF_LVQ_ENC
+    with_lvq_groups(per_lane, [&](auto G) {
+        hipLaunchKernelGGL((lvq_encode_kernel<decltype(G)::value, VEC, true>), grid, dim3(256), 0, st, x, n, d, coarse,
+                           assign, mu, B, sw, codes);
+    });
 }
 
 // ---------------------------------------------------------------- search
 constexpr int kIcWaves = 8;      // waves per scan workgroup: 512 rows per step
 constexpr int kIcTile = kIcWaves * 64;
-
-__global__ __launch_bounds__(64) void ivf_code_prep_kernel(const uint32_t* __restrict__ probe_l, int nlist, int nprobe,
-                                                           int64_t nqc, int S, int k, uint32_t* __restrict__ keys,
-                                                           float* __restrict__ pd, uint32_t* __restrict__ pi) {
-    int64_t a;
-    ivf_pair_prologue(probe_l, nlist, nprobe, nqc, S, k, keys, pd, pi, &a);
-}
 
 struct IcScan {
     IvfScan s;
@@ -217,10 +203,7 @@ ScanPolicy ic_policy(bool lvq) { return ScanPolicy{(lvq ? 1 : 2) + 1, 128, true}
 // Pairs per work item: the scan's query block, no wider than the pairs a list can expect (a
 // workgroup computes all QB chains of a row); 0: d does not fit the LDS.
 int ic_pairs_per_item(int64_t nq, int nlist, int nprobe, int d, bool lvq) {
-    int QB = scan_qb(d, ic_policy(lvq));
-    const int64_t per_list = ceil_div(std::max<int64_t>(nq, 1) * nprobe, nlist);
-    while (QB > 1 && QB / 2 >= per_list) QB /= 2;
-    return QB;
+    return ivf_pairs_per_item(scan_qb(d, ic_policy(lvq)), nq, nlist, nprobe);
 }
 
 // 0: d does not fit the LDS.
@@ -252,23 +235,19 @@ int ivf_code_search(const char* name, const float* q, int64_t nq, int d, const f
                     size_t workspace_bytes, float* dists, uint32_t* ids, void* stream) {
     using F = Fmt<FMT>;
     hipStream_t st = as_stream(stream);
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(list_codes);
-    const int rbytes = F::row_bytes(d);
-    const int wb = F::kWideWords * 4;
-    const int wide = addr % wb == 0 && rbytes % wb == 0;
-    const int narrow = addr % 4 == 0 && rbytes % 4 == 0;
+    const LoadModes lm = code_load_modes<FMT>(list_codes, d);
     return with_query_block(ic_pairs_per_item(nq, nlist, nprobe, d, F::kIsLvq), [&](auto QB) {
         constexpr int kQB = decltype(QB)::value;
         const IvfLayout L = ivf_layout(nq, nlist, nprobe, k, kQB, 0, 0, 16);
         return ivf_probed_search<kQB>(
             name, L, nq, nlist, nprobe, k, offsets, list_codes, list_ids, workspace, workspace_bytes, dists, ids, stream,
             [&](const IvfChunk& c) {
-                hipLaunchKernelGGL(ivf_code_prep_kernel, dim3((unsigned)c.pairs), dim3(64), 0, st,
+                hipLaunchKernelGGL(ivf_prep_kernel<64>, dim3((unsigned)c.pairs), dim3(64), 0, st,
                                    probe_l + c.a0 * nprobe, nlist, nprobe, c.nqc, L.S, k, c.keys, c.scan.pd, c.scan.pi);
                 return hipGetLastError();
             },
             [&](const IvfChunk& c, int64_t maxitems) {
-                const IcScan A{c.scan, q + c.a0 * d, coarse, ga, gb, d, metric, wide, narrow};
+                const IcScan A{c.scan, q + c.a0 * d, coarse, ga, gb, d, metric, lm.wide, lm.narrow};
                 return with_topk_regs(
                     k, [&](auto R) { return launch_ic_scan<FMT, decltype(R)::value, kQB>(A, maxitems, st); });
             });
@@ -315,8 +294,7 @@ extern "C" int mivq_ivf_sq_encode(const float* x, int64_t n, int32_t d, const fl
     MIVQ_REQUIRE(sq_bits_ok(nbits), MIVQ_ERR_INVALID, "num_bits must be 4, 8, or 16, got %d", nbits);
     if (n == 0) return MIVQ_OK;
     MIVQ_REQUIRE(x && coarse && assign && lo && den && codes, MIVQ_ERR_INVALID, "ivf_sq_encode: null pointer");
-    MIVQ_REQUIRE(nbits != 16 || reinterpret_cast<uintptr_t>(codes) % 2 == 0, MIVQ_ERR_INVALID,
-                 "ivf_sq_encode: 16-bit codes must be 2-byte aligned");
+    if (const int ra = sq16_aligned("ivf_sq_encode", nbits, codes)) return ra;
     const int64_t work = n * ((d + 7) / 8);
     hipLaunchKernelGGL((sq_encode_kernel<float, true>), dim3((unsigned)ceil_div(work, 256)), dim3(256), 0,
                        as_stream(stream), x, n, d, coarse, assign, lo, den, nbits, codes);
@@ -331,8 +309,7 @@ extern "C" int mivq_ivf_sq_decode(const void* codes, int64_t n, int32_t d, const
     MIVQ_REQUIRE(sq_bits_ok(nbits), MIVQ_ERR_INVALID, "num_bits must be 4, 8, or 16, got %d", nbits);
     if (n == 0) return MIVQ_OK;
     MIVQ_REQUIRE(codes && coarse && assign && lo && den && out, MIVQ_ERR_INVALID, "ivf_sq_decode: null pointer");
-    MIVQ_REQUIRE(nbits != 16 || reinterpret_cast<uintptr_t>(codes) % 2 == 0, MIVQ_ERR_INVALID,
-                 "ivf_sq_decode: 16-bit codes must be 2-byte aligned");
+    if (const int ra = sq16_aligned("ivf_sq_decode", nbits, codes)) return ra;
     hipLaunchKernelGGL((sq_decode_kernel<float, true>), dim3((unsigned)ceil_div(n * (int64_t)d, 256)), dim3(256), 0,
                        as_stream(stream), codes, n, d, coarse, assign, lo, den, nbits, out);
     return check_launch("ivf_sq_decode");
@@ -346,10 +323,7 @@ extern "C" int mivq_ivf_lvq_encode(const float* x, int64_t n, int32_t d, const f
     MIVQ_REQUIRE(lvq_bits_ok(nbits), MIVQ_ERR_INVALID, "num_bits must be in [1, 8], got %d", nbits);
     if (n == 0) return MIVQ_OK;
     MIVQ_REQUIRE(x && coarse && assign && mu && codes, MIVQ_ERR_INVALID, "ivf_lvq_encode: null pointer");
-    const int64_t cs = ((int64_t)d * nbits + 7) / 8 + 8;
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(codes);
-    int sw = 8;  // the widest store every group start of every row is aligned for
-    while (sw > 1 && (nbits % sw != 0 || cs % sw != 0 || addr % sw != 0)) sw >>= 1;
+    const int sw = lvq_store_width(codes, ((int64_t)d * nbits + 7) / 8 + 8, nbits);
     if (d % 4 == 0 && aligned16(x) && aligned16(mu) && aligned16(coarse))
         launch_ivf_lvq_encode<true>(x, n, d, coarse, assign, mu, nbits, sw, codes, as_stream(stream));
     else
@@ -395,16 +369,12 @@ extern "C" int mivq_ivf_sq_search(const float* q, int64_t nq, int32_t d, const f
     if (rc != MIVQ_OK || nq == 0) return rc;
     MIVQ_REQUIRE(q && coarse && probe_l && offsets && list_codes && list_ids && lo && den && dists && ids && workspace,
                  MIVQ_ERR_INVALID, "ivf_sq_search: null pointer");
-    MIVQ_REQUIRE(nbits != 16 || reinterpret_cast<uintptr_t>(list_codes) % 2 == 0, MIVQ_ERR_INVALID,
-                 "ivf_sq_search: 16-bit codes must be 2-byte aligned");
-    const uint8_t* c = static_cast<const uint8_t*>(list_codes);
-#define MIVQ_IVF_SQ_SEARCH(F)                                                                                        \
-    ivf_code_search<F>("ivf_sq_search", q, nq, d, coarse, nlist, probe_l, nprobe, offsets, c, list_ids, den, lo, metric, \
-                       k, workspace, workspace_bytes, dists, ids, stream)
-    if (nbits == 4) return MIVQ_IVF_SQ_SEARCH(kSq4);
-    if (nbits == 8) return MIVQ_IVF_SQ_SEARCH(kSq8);
-    return MIVQ_IVF_SQ_SEARCH(kSq16);
-#undef MIVQ_IVF_SQ_SEARCH
+    if (const int ra = sq16_aligned("ivf_sq_search", nbits, list_codes)) return ra;
+    return with_sq_bits(nbits, [&](auto F) {
+        return ivf_code_search<decltype(F)::value>("ivf_sq_search", q, nq, d, coarse, nlist, probe_l, nprobe, offsets,
+                                                   static_cast<const uint8_t*>(list_codes), list_ids, den, lo, metric, k,
+                                                   workspace, workspace_bytes, dists, ids, stream);
+    });
 }
 
 extern "C" int mivq_ivf_lvq_search(const float* q, int64_t nq, int32_t d, const float* coarse, int32_t nlist,
@@ -416,21 +386,9 @@ extern "C" int mivq_ivf_lvq_search(const float* q, int64_t nq, int32_t d, const 
     if (rc != MIVQ_OK || nq == 0) return rc;
     MIVQ_REQUIRE(q && coarse && probe_l && offsets && list_codes && list_ids && mu && dists && ids && workspace,
                  MIVQ_ERR_INVALID, "ivf_lvq_search: null pointer");
-#define MIVQ_IVF_LVQ_SEARCH(B)                                                                                        \
-    case B:                                                                                                           \
-        return ivf_code_search<kLvq + B - 1>("ivf_lvq_search", q, nq, d, coarse, nlist, probe_l, nprobe, offsets,      \
-                                             list_codes, list_ids, mu, nullptr, metric, k, workspace, workspace_bytes, \
-                                             dists, ids, stream)
-    switch (nbits) {
-        MIVQ_IVF_LVQ_SEARCH(1);
-        MIVQ_IVF_LVQ_SEARCH(2);
-        MIVQ_IVF_LVQ_SEARCH(3);
-        MIVQ_IVF_LVQ_SEARCH(4);
-        MIVQ_IVF_LVQ_SEARCH(5);
-        MIVQ_IVF_LVQ_SEARCH(6);
-        MIVQ_IVF_LVQ_SEARCH(7);
-        MIVQ_IVF_LVQ_SEARCH(8);
-        default: return MIVQ_ERR_INVALID;
-    }
-#undef MIVQ_IVF_LVQ_SEARCH
+    return with_lvq_bits(nbits, [&](auto F) {
+        return ivf_code_search<decltype(F)::value>("ivf_lvq_search", q, nq, d, coarse, nlist, probe_l, nprobe, offsets,
+                                                   list_codes, list_ids, mu, nullptr, metric, k, workspace, workspace_bytes,
+                                                   dists, ids, stream);
+    });
 }

@@ -1,5 +1,5 @@
 // ivf_internal.h — the probed-list driver of the searches over IVF lists of codes (ivf_rabitq.hip,
-// ivf_code.hip), and the workgroup scan it shares with ivf.hip.
+// ivf_code.hip, ivf_listpq.hip), and the workgroup scan it shares with ivf.hip.
 //
 // One search, per chunk of queries (ivf_probed_search):
 //   the caller's prep   one workgroup per (query, probe slot) pair: ivf_pair_prologue gives the pair
@@ -99,6 +99,16 @@ __device__ inline uint32_t ivf_pair_prologue(const uint32_t* __restrict__ probe_
     return l;
 }
 
+// The prep of a search whose pairs need the prologue and nothing else (ivf_code.hip,
+// ivf_listpq.hip): THREADS = its workgroup.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void ivf_prep_kernel(const uint32_t* __restrict__ probe_l, int nlist, int nprobe,
+                                                           int64_t nqc, int S, int k, uint32_t* __restrict__ keys,
+                                                           float* __restrict__ pd, uint32_t* __restrict__ pi) {
+    int64_t a;
+    ivf_pair_prologue(probe_l, nlist, nprobe, nqc, S, k, keys, pd, pi, &a);
+}
+
 // What every scan over probed lists takes; the caller's argument struct embeds it.
 struct IvfScan {
     int64_t* poff;           // sorted-pair offsets per list
@@ -187,6 +197,15 @@ inline IvfLayout ivf_layout(int64_t nq, int nlist, int nprobe, int k, int ppi, s
         L = build(nqc);
     }
     return L;
+}
+
+// Pairs per work item: max_qb (a power of two; 0 stays 0), narrowed to the pairs a list can
+// expect, since a scan workgroup computes the chains of all its pairs for every row.
+inline int ivf_pairs_per_item(int max_qb, int64_t nq, int nlist, int nprobe) {
+    int QB = max_qb;
+    const int64_t per_list = ceil_div(std::max<int64_t>(nq, 1) * nprobe, nlist);
+    while (QB > 1 && QB / 2 >= per_list) QB /= 2;
+    return QB;
 }
 
 // The argument checks of the searches and of their workspace queries.

@@ -10,7 +10,7 @@
 // workspace region:
 //
 //   ivf_listpq_decode_kernel  thread = output float: the sub-centroid's float plus the centroid's.
-//   ivf_listpq_prep_kernel    the driver's pair prologue, nothing else.
+//   ivf_prep_kernel           (ivf_internal.h) the driver's pair prologue, nothing else.
 //   ivf_listpq_table_kernel   grid (item bound, groups of table units), 256 threads, thread =
 //                             table entry (m, j): the list's codebook row is read once per work
 //                             item and serves its QB pairs, whose query slices and the centroid
@@ -22,12 +22,12 @@
 //                             preserves it.  WaveTopK selection inside the scan, the waves' lists
 //                             merged in LDS into one list per (pair, range).
 // The search runs on the probed-list driver (ivf_internal.h).
+#include "adc_internal.h"
 #include "ivf_internal.h"
 #include "mivq_common.h"
 #include "topk.h"
 
 #include <algorithm>
-#include <type_traits>
 
 namespace mivq {
 namespace {
@@ -64,14 +64,6 @@ __global__ __launch_bounds__(256) void ivf_listpq_decode_kernel(const uint8_t* _
 }
 
 // ---------------------------------------------------------------- search
-__global__ __launch_bounds__(64) void ivf_listpq_prep_kernel(const uint32_t* __restrict__ probe_l, int nlist,
-                                                             int nprobe, int64_t nqc, int S, int k,
-                                                             uint32_t* __restrict__ keys, float* __restrict__ pd,
-                                                             uint32_t* __restrict__ pi) {
-    int64_t a;
-    ivf_pair_prologue(probe_l, nlist, nprobe, nqc, S, k, keys, pd, pi, &a);
-}
-
 struct LpTab {
     IvfScan s;
     const float* q;       // (nqc, d) the chunk's queries
@@ -316,23 +308,6 @@ __global__ __launch_bounds__(kLpWaves * 64) void ivf_listpq_scan_kernel(const Lp
 }
 
 // ---------------------------------------------------------------- host side
-// Pairs per work item: no wider than the pairs a list can expect.
-int lp_pairs_per_item(int64_t nq, int nlist, int nprobe) {
-    int QB = kLpMaxQB;
-    const int64_t per_list = ceil_div(std::max<int64_t>(nq, 1) * nprobe, nlist);
-    while (QB > 1 && QB / 2 >= per_list) QB /= 2;
-    return QB;
-}
-
-template <typename F>
-auto with_pair_block(int QB, F&& f) {
-    switch (QB) {
-        case 4: return f(std::integral_constant<int, 4>{});
-        case 2: return f(std::integral_constant<int, 2>{});
-        default: return f(std::integral_constant<int, 1>{});
-    }
-}
-
 // The table bytes of a pair are counted in the chunk estimate: the queries per chunk shrink with
 // M * ksub, so the workspace stays under the driver's cap (one query per chunk at the least).
 IvfLayout lp_layout(int64_t nq, int nlist, int nprobe, int k, int QB, int M, int nbits) {
@@ -404,7 +379,7 @@ extern "C" int mivq_ivf_listpq_decode(const uint8_t* codes, int64_t n, int32_t d
 extern "C" size_t mivq_ivf_listpq_search_workspace_bytes(int64_t nq, int64_t n, int32_t nlist, int32_t nprobe,
                                                          int32_t d, int32_t M, int32_t nbits, int32_t k) {
     if (!ivf_shape_ok(nq, n, nlist, nprobe, d, k) || !lp_shape_ok(d, M, nbits)) return 0;
-    return lp_layout(nq, nlist, nprobe, k, lp_pairs_per_item(nq, nlist, nprobe), M, nbits).total;
+    return lp_layout(nq, nlist, nprobe, k, ivf_pairs_per_item(kLpMaxQB, nq, nlist, nprobe), M, nbits).total;
 }
 
 extern "C" int mivq_ivf_listpq_search(const float* q, int64_t nq, int32_t d, int32_t M, int32_t nbits,
@@ -422,13 +397,13 @@ extern "C" int mivq_ivf_listpq_search(const float* q, int64_t nq, int32_t d, int
     MIVQ_REQUIRE(q && codebooks && coarse && probe_l && offsets && list_codes && list_ids && dists && ids && workspace,
                  MIVQ_ERR_INVALID, "%s: null pointer", name);
     hipStream_t st = as_stream(stream);
-    return with_pair_block(lp_pairs_per_item(nq, nlist, nprobe), [&](auto QB) {
+    return with_query_block<kLpMaxQB>(ivf_pairs_per_item(kLpMaxQB, nq, nlist, nprobe), [&](auto QB) {
         constexpr int kQB = decltype(QB)::value;
         const IvfLayout L = lp_layout(nq, nlist, nprobe, k, kQB, M, nbits);
         return ivf_probed_search<kQB>(
             name, L, nq, nlist, nprobe, k, offsets, list_codes, list_ids, workspace, workspace_bytes, dists, ids, stream,
             [&](const IvfChunk& c) {
-                hipLaunchKernelGGL(ivf_listpq_prep_kernel, dim3((unsigned)c.pairs), dim3(64), 0, st,
+                hipLaunchKernelGGL(ivf_prep_kernel<64>, dim3((unsigned)c.pairs), dim3(64), 0, st,
                                    probe_l + c.a0 * nprobe, nlist, nprobe, c.nqc, L.S, k, c.keys, c.scan.pd, c.scan.pi);
                 return hipGetLastError();
             },

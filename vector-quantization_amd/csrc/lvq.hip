@@ -85,23 +85,16 @@ __global__ __launch_bounds__(256) void column_mean_kernel(const float* __restric
     if (tid < kCmCols && c0 + tid < d) mean[c0 + tid] = __fdiv_rn(acc, (float)n);
 }
 
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 template <bool VEC>
 void launch_lvq_encode(const float* x, int64_t n, int d, const float* mu, int B, int sw, uint8_t* codes, hipStream_t st) {
     const int per_lane = (int)ceil_div((d + 7) / 8, 64);
     // 32 workgroups per CU at most: a wave walks several rows with its part of mu in registers
     // (and grid.x stays far below its limit for any n)
     const dim3 grid((unsigned)std::min<int64_t>(ceil_div(n, 4), (int64_t)device_cus() * 32));
-#define MIVQ_LVQ_ENC(G) \
-    hipLaunchKernelGGL((lvq_encode_kernel<G, VEC, false>), grid, dim3(256), 0, st, x, n, d, nullptr, nullptr, mu, B, sw, codes)
-    if (per_lane <= 1) MIVQ_LVQ_ENC(1);
-    else if (per_lane == 2) MIVQ_LVQ_ENC(2);
-    else if (per_lane == 3) MIVQ_LVQ_ENC(3);
-    else if (per_lane == 4) MIVQ_LVQ_ENC(4);
-    else if (per_lane <= kLvqMaxRegGroups) MIVQ_LVQ_ENC(kLvqMaxRegGroups);
-    else MIVQ_LVQ_ENC(0);
-#undef MIVQ_LVQ_ENC
+    with_lvq_groups(per_lane, [&](auto G) {
+        hipLaunchKernelGGL((lvq_encode_kernel<decltype(G)::value, VEC, false>), grid, dim3(256), 0, st, x, n, d, nullptr,
+                           nullptr, mu, B, sw, codes);
+    });
 }
 
 int lvq_check(const char* name, int64_t n, int32_t d, int32_t nbits) {
@@ -131,10 +124,7 @@ extern "C" int mivq_lvq_encode(const float* x, int64_t n, int32_t d, const float
     const int rc = lvq_check("lvq_encode", n, d, nbits);
     if (rc != MIVQ_OK || n == 0) return rc;
     MIVQ_REQUIRE(x && mu && codes, MIVQ_ERR_INVALID, "lvq_encode: null pointer");
-    const int64_t cs = ((int64_t)d * nbits + 7) / 8 + 8;
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(codes);
-    int sw = 8;  // the widest store every group start of every row is aligned for
-    while (sw > 1 && (nbits % sw != 0 || cs % sw != 0 || addr % sw != 0)) sw >>= 1;
+    const int sw = lvq_store_width(codes, ((int64_t)d * nbits + 7) / 8 + 8, nbits);
     if (d % 4 == 0 && aligned16(x) && aligned16(mu))
         launch_lvq_encode<true>(x, n, d, mu, nbits, sw, codes, as_stream(stream));
     else

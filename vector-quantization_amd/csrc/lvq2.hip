@@ -408,9 +408,8 @@ __global__ __launch_bounds__(kRerankWaves * 64) void rerank_lvq2_kernel(
 
 // the widest of the three ways every row start of an array is aligned for
 int load_mode(const void* base, int64_t stride, int wide_bytes, bool wide_ok) {
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(base);
-    if (wide_ok && addr % wide_bytes == 0 && stride % wide_bytes == 0) return kWide;
-    return addr % 4 == 0 && stride % 4 == 0 ? k4B : kBytes;
+    const LoadModes lm = load_modes(base, stride, wide_bytes);
+    return wide_ok && lm.wide ? kWide : lm.narrow ? k4B : kBytes;
 }
 
 template <int B1, int B2>
@@ -441,33 +440,19 @@ int rerank_lvq2(const float* q, int64_t nq, const uint32_t* cand, int64_t r, con
 }
 
 // ---------------------------------------------------------------- host
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
-// the widest store every group start of every row of an array is aligned for
-int store_width(const void* base, int64_t stride, int B) {
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(base);
-    int sw = 8;
-    while (sw > 1 && (B % sw != 0 || stride % sw != 0 || addr % sw != 0)) sw >>= 1;
-    return sw;
-}
-
 template <bool VEC>
 void launch_lvq2_encode(const float* x, int64_t n, int d, const float* mu, int B1, int B2, uint8_t* codes1,
                         uint8_t* codes2, hipStream_t st) {
     const int per_lane = (int)ceil_div((d + 7) / 8, 64);
-    const int sw1 = store_width(codes1, ((int64_t)d * B1 + 7) / 8 + 8, B1);
-    const int sw2 = store_width(codes2, ((int64_t)d * B2 + 7) / 8, B2);
+    const int sw1 = lvq_store_width(codes1, ((int64_t)d * B1 + 7) / 8 + 8, B1);
+    const int sw2 = lvq_store_width(codes2, ((int64_t)d * B2 + 7) / 8, B2);
     // 32 workgroups per CU at most, as launch_lvq_encode
     const dim3 grid((unsigned)std::min<int64_t>(ceil_div(n, 4), (int64_t)device_cus() * 32));
-#define MIVQ_LVQ2_ENC(G) \
-    hipLaunchKernelGGL((lvq2_encode_kernel<G, VEC>), grid, dim3(256), 0, st, x, n, d, mu, B1, B2, sw1, sw2, codes1, codes2)
     // (no G = 1: that instantiation alone spilled 18 SGPRs; at d <= 512 the second group is predicated off)
-    if (per_lane <= 2) MIVQ_LVQ2_ENC(2);
-    else if (per_lane == 3) MIVQ_LVQ2_ENC(3);
-    else if (per_lane == 4) MIVQ_LVQ2_ENC(4);
-    else if (per_lane <= kLvqMaxRegGroups) MIVQ_LVQ2_ENC(kLvqMaxRegGroups);
-    else MIVQ_LVQ2_ENC(0);
-#undef MIVQ_LVQ2_ENC
+    with_lvq_groups<2>(per_lane, [&](auto G) {
+        hipLaunchKernelGGL((lvq2_encode_kernel<decltype(G)::value, VEC>), grid, dim3(256), 0, st, x, n, d, mu, B1, B2, sw1,
+                           sw2, codes1, codes2);
+    });
 }
 
 int lvq2_bits_check(int32_t nbits1, int32_t nbits2) {
@@ -530,21 +515,10 @@ extern "C" int mivq_rerank_lvq2(const float* q, int64_t nq, const uint32_t* cand
                          workspace_bytes, dists, ids, st, &done);
     if (rc != MIVQ_OK || done) return rc;
     MIVQ_REQUIRE(codes1 && codes2 && mu, MIVQ_ERR_INVALID, "rerank_lvq2: null pointer");
-#define MIVQ_LVQ2_RERANK(B)                                                                                               \
-    case B:                                                                                                               \
-        if (nbits2 == 4)                                                                                                  \
-            return rerank_lvq2<B, 4>(q, nq, cand, r, codes1, codes2, n, d, mu, metric, k, id_offset, workspace, dists, ids, st); \
-        return rerank_lvq2<B, 8>(q, nq, cand, r, codes1, codes2, n, d, mu, metric, k, id_offset, workspace, dists, ids, st)
-    switch (nbits1) {
-        MIVQ_LVQ2_RERANK(1);
-        MIVQ_LVQ2_RERANK(2);
-        MIVQ_LVQ2_RERANK(3);
-        MIVQ_LVQ2_RERANK(4);
-        MIVQ_LVQ2_RERANK(5);
-        MIVQ_LVQ2_RERANK(6);
-        MIVQ_LVQ2_RERANK(7);
-        MIVQ_LVQ2_RERANK(8);
-        default: return MIVQ_ERR_INVALID;
-    }
-#undef MIVQ_LVQ2_RERANK
+    return with_lvq_bits(nbits1, [&](auto F) {
+        constexpr int B1 = Fmt<decltype(F)::value>::kB;
+        if (nbits2 == 4)
+            return rerank_lvq2<B1, 4>(q, nq, cand, r, codes1, codes2, n, d, mu, metric, k, id_offset, workspace, dists, ids, st);
+        return rerank_lvq2<B1, 8>(q, nq, cand, r, codes1, codes2, n, d, mu, metric, k, id_offset, workspace, dists, ids, st);
+    });
 }

@@ -30,6 +30,7 @@ int device_cus();
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 // ---------------------------------------------------------------- wave reductions (all 64 lanes)
 __device__ __forceinline__ float wave_min(float v) {

@@ -274,7 +274,6 @@ __global__ __launch_bounds__(kRaThreads) void ra_finish_kernel(const double* __r
     }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Rows per workgroup: as many as the 64 KiB of LDS hold beside the kernel's other use of it, at
 // most the kernel's tile (>= 1 for every code_size <= kRaMaxCode).

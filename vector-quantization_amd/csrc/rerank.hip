@@ -80,15 +80,11 @@ hipError_t launch_rerank(const float* q, int64_t nq, const uint32_t* cand, int64
     auto kern = rerank_kernel<FMT, R>;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return e;
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(codes);
-    const int rb = F::row_bytes(d);
-    const int wb = F::kWideWords * 4;
-    const int wide = addr % wb == 0 && rb % wb == 0;
-    const int narrow = addr % 4 == 0 && rb % 4 == 0;
+    const LoadModes lm = code_load_modes<FMT>(codes, d);
     // whole waves per slice, so that no wave straddles two slices
     const int64_t slice_slots = ceil_div(ceil_div(r, L.S), 64) * 64;
     hipLaunchKernelGGL(kern, dim3((unsigned)nq, (unsigned)L.S), dim3(kRerankWaves * 64), smem, st, q, cand, r, codes, n, d,
-                       ga, gb, metric, k, (uint32_t)id_offset, slice_slots, wide, narrow, pd, pi);
+                       ga, gb, metric, k, (uint32_t)id_offset, slice_slots, lm.wide, lm.narrow, pd, pi);
     return hipGetLastError();
 }
 
@@ -152,14 +148,11 @@ extern "C" int mivq_rerank_sq(const float* q, int64_t nq, const uint32_t* cand, 
                                    workspace_bytes, dists, ids, st, &done);
     if (rc != MIVQ_OK || done) return rc;
     MIVQ_REQUIRE(codes && lo && den, MIVQ_ERR_INVALID, "rerank_sq: null pointer");
-    MIVQ_REQUIRE(nbits != 16 || reinterpret_cast<uintptr_t>(codes) % 2 == 0, MIVQ_ERR_INVALID,
-                 "rerank_sq: 16-bit codes must be 2-byte aligned");
-    const uint8_t* c = static_cast<const uint8_t*>(codes);
-    if (nbits == 4)
-        return rerank<kSq4>("rerank_sq", q, nq, cand, r, c, n, d, den, lo, metric, k, id_offset, workspace, dists, ids, st);
-    if (nbits == 8)
-        return rerank<kSq8>("rerank_sq", q, nq, cand, r, c, n, d, den, lo, metric, k, id_offset, workspace, dists, ids, st);
-    return rerank<kSq16>("rerank_sq", q, nq, cand, r, c, n, d, den, lo, metric, k, id_offset, workspace, dists, ids, st);
+    if (const int ra = sq16_aligned("rerank_sq", nbits, codes)) return ra;
+    return with_sq_bits(nbits, [&](auto F) {
+        return rerank<decltype(F)::value>("rerank_sq", q, nq, cand, r, static_cast<const uint8_t*>(codes), n, d, den, lo,
+                                          metric, k, id_offset, workspace, dists, ids, st);
+    });
 }
 
 extern "C" int mivq_rerank_lvq(const float* q, int64_t nq, const uint32_t* cand, int64_t r, const uint8_t* codes,
@@ -174,20 +167,8 @@ extern "C" int mivq_rerank_lvq(const float* q, int64_t nq, const uint32_t* cand,
                                    workspace_bytes, dists, ids, st, &done);
     if (rc != MIVQ_OK || done) return rc;
     MIVQ_REQUIRE(codes && mu, MIVQ_ERR_INVALID, "rerank_lvq: null pointer");
-#define MIVQ_LVQ_RERANK(B)                                                                                            \
-    case B:                                                                                                           \
-        return rerank<kLvq + B - 1>("rerank_lvq", q, nq, cand, r, codes, n, d, mu, nullptr, metric, k, id_offset, workspace, \
-                                    dists, ids, st)
-    switch (nbits) {
-        MIVQ_LVQ_RERANK(1);
-        MIVQ_LVQ_RERANK(2);
-        MIVQ_LVQ_RERANK(3);
-        MIVQ_LVQ_RERANK(4);
-        MIVQ_LVQ_RERANK(5);
-        MIVQ_LVQ_RERANK(6);
-        MIVQ_LVQ_RERANK(7);
-        MIVQ_LVQ_RERANK(8);
-        default: return MIVQ_ERR_UNSUPPORTED;
-    }
-#undef MIVQ_LVQ_RERANK
+    return with_lvq_bits(nbits, [&](auto F) {
+        return rerank<decltype(F)::value>("rerank_lvq", q, nq, cand, r, codes, n, d, mu, nullptr, metric, k, id_offset,
+                                          workspace, dists, ids, st);
+    });
 }

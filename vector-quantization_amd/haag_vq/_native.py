@@ -253,6 +253,32 @@ def workspace(nbytes: int, device: torch.device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+def _search_call(entry: str, size_args: tuple, head: tuple, nq: int, k: int, device: torch.device, tail: tuple = (),
+                 out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The tail of every search wrapper: the outputs (dists f32 (nq, k), ids int32 (nq, k) holding
+    uint32 ids; `out`: the rows of a caller that goes through its queries in ranges), the workspace
+    <entry>_workspace_bytes(*size_args) asks for, and the call
+    <entry>(*head, ws, ws_bytes, dists, ids, *tail, stream)."""
+    if out is None:
+        out = (torch.empty((nq, k), dtype=torch.float32, device=device),
+               torch.empty((nq, k), dtype=torch.int32, device=device))
+    ws = workspace(getattr(load_library(), f"{entry}_workspace_bytes")(*size_args), device)
+    _call(entry, *head, _ptr(ws), ws.numel(), _ptr(out[0]), _ptr(out[1]), *tail, _stream())
+    return out
+
+
+def _check_query_width(q: torch.Tensor, d: int) -> None:
+    if q.shape[1] != d:
+        raise ValueError(f"codes have d={d}, queries d={q.shape[1]}")
+
+
+def _check_dim_vector(t: torch.Tensor, name: str, d: int, what: str) -> None:
+    """A per-dimension f32 vector of d entries."""
+    _check(t, name, torch.float32, 1)
+    if t.numel() != d:
+        raise ValueError(f"{what}: {name} has {t.numel()} entries, expected d={d}")
+
+
 # ----------------------------------------------------------------- device info
 def device_info(device: int = 0) -> dict:
     name = ctypes.create_string_buffer(64)
@@ -615,9 +641,9 @@ def rabitq_search(codes: torch.Tensor, d: int, centroid: Optional[torch.Tensor],
     step = MAX_QUERIES_PER_CALL if generic else max(nq, 1)
     for s in range(0, max(nq, 1), step):
         c = min(nq, s + step) - s
-        ws = workspace(load_library().mivq_rabitq_search_workspace_bytes(c, n, d, k), q.device)
-        _call("mivq_rabitq_search", _ptr(codes), n, d, _ptr(centroid), _ptr(q[s:s + c]), c, qb, metric, k, id_offset,
-              _ptr(ws), ws.numel(), _ptr(dists[s:s + c]), _ptr(ids[s:s + c]), _stream())
+        _search_call("mivq_rabitq_search", (c, n, d, k),
+                     (_ptr(codes), n, d, _ptr(centroid), _ptr(q[s:s + c]), c, qb, metric, k, id_offset),
+                     c, k, q.device, out=(dists[s:s + c], ids[s:s + c]))
     return dists, ids
 
 
@@ -753,12 +779,9 @@ def extrabitq_flat_search(qy: torch.Tensor, codes: torch.Tensor, levels: torch.T
     if levels.numel() != 1 << nbits:
         raise ValueError(f"extrabitq: levels has {levels.numel()} entries, expected {1 << nbits}")
     nq, n = qy.shape[0], codes.shape[0]
-    dists = torch.empty((nq, k), dtype=torch.float32, device=qy.device)
-    ids = torch.empty((nq, k), dtype=torch.int32, device=qy.device)
-    ws = workspace(load_library().mivq_extrabitq_flat_search_workspace_bytes(nq, n, d, k), qy.device)
-    _call("mivq_extrabitq_flat_search", _ptr(qy), nq, _ptr(codes), n, d, _ptr(levels), nbits, metric, k, id_offset,
-          _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids), _stream())
-    return dists, ids
+    return _search_call("mivq_extrabitq_flat_search", (nq, n, d, k),
+                        (_ptr(qy), nq, _ptr(codes), n, d, _ptr(levels), nbits, metric, k, id_offset),
+                        nq, k, qy.device)
 
 
 # ----------------------------------------------------------------- rank-aware quantizer
@@ -943,19 +966,15 @@ def rankaware_flat_search(qy: torch.Tensor, codes: torch.Tensor, st: RankAwareSt
     _check(qy, "qy", torch.float32, 2)
     if not qy.is_contiguous():
         raise ValueError("qy must be contiguous")
-    if qy.shape[1] != d:
-        raise ValueError(f"codes have d={d}, queries d={qy.shape[1]}")
+    _check_query_width(qy, d)
     lv32 = rankaware_lv32(st)
     _check(lv32, "lv32", torch.float32, 1)
     if lv32.numel() != st.lv.numel():
         raise ValueError(f"rankaware: lv32 has {lv32.numel()} entries, lv {st.lv.numel()}")
     nq, n = qy.shape[0], codes.shape[0]
-    dists = torch.empty((nq, k), dtype=torch.float32, device=qy.device)
-    ids = torch.empty((nq, k), dtype=torch.int32, device=qy.device)
-    ws = workspace(load_library().mivq_rankaware_flat_search_workspace_bytes(nq, n, d, st.code_size, k), qy.device)
-    _call("mivq_rankaware_flat_search", _ptr(qy), nq, _ptr(codes), n, d, _ptr(lv32), _ptr(st.lv_off), _ptr(st.pos),
-          _ptr(st.width), st.code_size, metric, k, id_offset, _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids), _stream())
-    return dists, ids
+    return _search_call("mivq_rankaware_flat_search", (nq, n, d, st.code_size, k),
+                        (_ptr(qy), nq, _ptr(codes), n, d, _ptr(lv32), _ptr(st.lv_off), _ptr(st.pos), _ptr(st.width),
+                         st.code_size, metric, k, id_offset), nq, k, qy.device)
 
 
 # ----------------------------------------------------------------- fitted 1-D codebooks
@@ -1077,13 +1096,8 @@ def adc_search(lut: torch.Tensor, codes_u8: torch.Tensor, k: int, nbits: int,
     n = codes_u8.shape[0]
     if codes_u8.shape[1] != M:
         raise ValueError(f"codes have {codes_u8.shape[1]} sub-codes, LUT has M={M}")
-    dists = torch.empty((nq, k), dtype=torch.float32, device=lut.device)
-    ids = torch.empty((nq, k), dtype=torch.int32, device=lut.device)
-    nb = load_library().mivq_adc_search_workspace_bytes(nq, n, M, nbits, k)
-    ws = workspace(nb, lut.device)
-    _call("mivq_adc_search", _ptr(lut), nq, _ptr(codes_u8), n, M, nbits, k, id_offset, _ptr(ws), ws.numel(),
-          _ptr(dists), _ptr(ids), flags, _stream())
-    return dists, ids
+    return _search_call("mivq_adc_search", (nq, n, M, nbits, k), (_ptr(lut), nq, _ptr(codes_u8), n, M, nbits, k, id_offset),
+                        nq, k, lut.device, tail=(flags,))
 
 
 def flat_search(q: torch.Tensor, x: torch.Tensor, k: int, metric: int = METRIC_L2,
@@ -1094,13 +1108,8 @@ def flat_search(q: torch.Tensor, x: torch.Tensor, k: int, metric: int = METRIC_L
     n = x.shape[0]
     if x.shape[1] != d:
         raise ValueError(f"database has d={x.shape[1]}, queries d={d}")
-    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
-    nb = load_library().mivq_flat_search_workspace_bytes(nq, n, d, k)
-    ws = workspace(nb, q.device)
-    _call("mivq_flat_search", _ptr(q), nq, _ptr(x), n, d, metric, k, id_offset, _ptr(ws), ws.numel(),
-          _ptr(dists), _ptr(ids), _stream())
-    return dists, ids
+    return _search_call("mivq_flat_search", (nq, n, d, k), (_ptr(q), nq, _ptr(x), n, d, metric, k, id_offset),
+                        nq, k, q.device)
 
 
 def _sq_code_check(codes: torch.Tensor, d: int, nbits: int, what: str) -> None:
@@ -1125,15 +1134,11 @@ def sq_flat_search(q: torch.Tensor, codes: torch.Tensor, d: int, lo: torch.Tenso
     _check(den, "den", torch.float32, 1)
     if lo.numel() != d or den.numel() != d:
         raise ValueError(f"sq_flat_search: min/max have {lo.numel()}/{den.numel()} entries, expected d={d}")
-    if q.shape[1] != d:
-        raise ValueError(f"codes have d={d}, queries d={q.shape[1]}")
+    _check_query_width(q, d)
     nq, n = q.shape[0], codes.shape[0]
-    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
-    ws = workspace(load_library().mivq_sq_flat_search_workspace_bytes(nq, n, d, k), q.device)
-    _call("mivq_sq_flat_search", _ptr(q), nq, _ptr(codes), n, d, _ptr(lo), _ptr(den), nbits, metric, k, id_offset,
-          _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids), _stream())
-    return dists, ids
+    return _search_call("mivq_sq_flat_search", (nq, n, d, k),
+                        (_ptr(q), nq, _ptr(codes), n, d, _ptr(lo), _ptr(den), nbits, metric, k, id_offset),
+                        nq, k, q.device)
 
 
 def rabitq_flat_search(q: torch.Tensor, codes: torch.Tensor, d: int, centroid: Optional[torch.Tensor], k: int,
@@ -1148,18 +1153,11 @@ def rabitq_flat_search(q: torch.Tensor, codes: torch.Tensor, d: int, centroid: O
     _check(codes, "codes", torch.uint8, 2)
     _check(q, "q", torch.float32, 2)
     if centroid is not None:
-        _check(centroid, "centroid", torch.float32, 1)
-        if centroid.numel() != d:
-            raise ValueError(f"rabitq_flat_search: centroid has {centroid.numel()} entries, expected d={d}")
-    if q.shape[1] != d:
-        raise ValueError(f"codes have d={d}, queries d={q.shape[1]}")
+        _check_dim_vector(centroid, "centroid", d, "rabitq_flat_search")
+    _check_query_width(q, d)
     nq, n = q.shape[0], codes.shape[0]
-    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
-    ws = workspace(load_library().mivq_rabitq_flat_search_workspace_bytes(nq, n, d, k), q.device)
-    _call("mivq_rabitq_flat_search", _ptr(q), nq, _ptr(codes), n, d, _ptr(centroid), metric, k, id_offset, _ptr(ws),
-          ws.numel(), _ptr(dists), _ptr(ids), _stream())
-    return dists, ids
+    return _search_call("mivq_rabitq_flat_search", (nq, n, d, k),
+                        (_ptr(q), nq, _ptr(codes), n, d, _ptr(centroid), metric, k, id_offset), nq, k, q.device)
 
 
 def lvq_flat_search(q: torch.Tensor, codes: torch.Tensor, mu: torch.Tensor, nbits: int, k: int,
@@ -1170,15 +1168,10 @@ def lvq_flat_search(q: torch.Tensor, codes: torch.Tensor, mu: torch.Tensor, nbit
     d = mu.numel()
     _lvq_code_check(codes, d, nbits, "lvq_flat_search")
     _check(q, "q", torch.float32, 2)
-    if q.shape[1] != d:
-        raise ValueError(f"codes have d={d}, queries d={q.shape[1]}")
+    _check_query_width(q, d)
     nq, n = q.shape[0], codes.shape[0]
-    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
-    ws = workspace(load_library().mivq_lvq_flat_search_workspace_bytes(nq, n, d, k), q.device)
-    _call("mivq_lvq_flat_search", _ptr(q), nq, _ptr(codes), n, d, _ptr(mu), nbits, metric, k, id_offset, _ptr(ws),
-          ws.numel(), _ptr(dists), _ptr(ids), _stream())
-    return dists, ids
+    return _search_call("mivq_lvq_flat_search", (nq, n, d, k),
+                        (_ptr(q), nq, _ptr(codes), n, d, _ptr(mu), nbits, metric, k, id_offset), nq, k, q.device)
 
 
 def rerank(kind: str, q: torch.Tensor, cand: torch.Tensor, store: torch.Tensor, params: Tuple[torch.Tensor, ...],
@@ -1202,9 +1195,7 @@ def rerank(kind: str, q: torch.Tensor, cand: torch.Tensor, store: torch.Tensor, 
     if len(params) != len(names):
         raise ValueError(f"rerank: {kind} takes the parameters {names}")
     for name, t in zip(names, params):
-        _check(t, name, torch.float32, 1)
-        if t.numel() != d:
-            raise ValueError(f"rerank: {name} has {t.numel()} entries, expected d={d}")
+        _check_dim_vector(t, name, d, "rerank")
     if kind == "f32":
         _check(store, "x", torch.float32, 2)
         if store.shape[1] != d:
@@ -1219,12 +1210,9 @@ def rerank(kind: str, q: torch.Tensor, cand: torch.Tensor, store: torch.Tensor, 
         _lvq_code_check(store, d, nbits, "rerank")
         extra = (_ptr(params[0]), nbits)
     n = store.shape[0]
-    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
-    ws = workspace(getattr(load_library(), f"mivq_rerank_{kind}_workspace_bytes")(nq, r, k), q.device)
-    _call(f"mivq_rerank_{kind}", _ptr(q), nq, _ptr(cand), r, _ptr(store), n, d, *extra, metric, k, id_offset, _ptr(ws),
-          ws.numel(), _ptr(dists), _ptr(ids), _stream())
-    return dists, ids
+    return _search_call(f"mivq_rerank_{kind}", (nq, r, k),
+                        (_ptr(q), nq, _ptr(cand), r, _ptr(store), n, d, *extra, metric, k, id_offset),
+                        nq, k, q.device)
 
 
 def rerank_lvq2(q: torch.Tensor, cand: torch.Tensor, codes1: torch.Tensor, codes2: torch.Tensor, mu: torch.Tensor,
@@ -1234,21 +1222,16 @@ def rerank_lvq2(q: torch.Tensor, cand: torch.Tensor, codes1: torch.Tensor, codes
     flat_search(q, lvq2_decode(codes1, codes2)) for the candidates, bit for bit."""
     _check(q, "q", torch.float32, 2)
     _check(cand, "cand", torch.int32, 2)
-    _check(mu, "mu", torch.float32, 1)
     nq, d = q.shape
     r = cand.shape[1]
     if cand.shape[0] != nq:
         raise ValueError(f"rerank_lvq2: {cand.shape[0]} candidate lists for {nq} queries")
-    if mu.numel() != d:
-        raise ValueError(f"rerank_lvq2: mu has {mu.numel()} entries, expected d={d}")
+    _check_dim_vector(mu, "mu", d, "rerank_lvq2")
     _lvq2_code_check(codes1, codes2, d, nbits1, nbits2, "rerank_lvq2")
     n = codes1.shape[0]
-    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
-    ws = workspace(load_library().mivq_rerank_lvq2_workspace_bytes(nq, r, k), q.device)
-    _call("mivq_rerank_lvq2", _ptr(q), nq, _ptr(cand), r, _ptr(codes1), _ptr(codes2), n, d, _ptr(mu), nbits1, nbits2,
-          metric, k, id_offset, _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids), _stream())
-    return dists, ids
+    return _search_call("mivq_rerank_lvq2", (nq, r, k),
+                        (_ptr(q), nq, _ptr(cand), r, _ptr(codes1), _ptr(codes2), n, d, _ptr(mu), nbits1, nbits2, metric, k,
+                         id_offset), nq, k, q.device)
 
 
 def topk_merge(dists: torch.Tensor, ids: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -1381,11 +1364,10 @@ def ivfpq_search(lut: torch.Tensor, probe_d: torch.Tensor, probe_l: torch.Tensor
     # independent, so ranges of them give the rows of one call
     for s in range(0, max(nq, 1), MAX_QUERIES_PER_CALL):
         c = min(nq, s + MAX_QUERIES_PER_CALL) - s
-        nb = load_library().mivq_ivfpq_search_workspace_bytes(c, nprobe, k)
-        ws = workspace(nb, lut.device)
-        _call("mivq_ivfpq_search", _ptr(lut[s:s + c]), c, M, nbits, _ptr(probe_d[s:s + c]), _ptr(probe_l[s:s + c]),
-              nprobe, nlist, _ptr(offsets), _ptr(list_codes), _ptr(list_ids), _ptr(tau), metric, k, _ptr(ws),
-              ws.numel(), _ptr(dists[s:s + c]), _ptr(ids[s:s + c]), _stream())
+        _search_call("mivq_ivfpq_search", (c, nprobe, k),
+                     (_ptr(lut[s:s + c]), c, M, nbits, _ptr(probe_d[s:s + c]), _ptr(probe_l[s:s + c]), nprobe, nlist,
+                      _ptr(offsets), _ptr(list_codes), _ptr(list_ids), _ptr(tau), metric, k),
+                     c, k, lut.device, out=(dists[s:s + c], ids[s:s + c]))
     return dists, ids
 
 
@@ -1424,13 +1406,9 @@ def _ivf_list_search(entry: str, what: str, q: torch.Tensor, coarse: torch.Tenso
     n = list_codes.shape[0]
     if probe_l.shape[0] != nq or offsets.shape[0] != nlist + 1 or list_ids.shape[0] != n:
         raise ValueError(f"{what}: shape mismatch")
-    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
-    size_fn = getattr(load_library(), f"mivq_ivf_{entry}_search_workspace_bytes")
-    ws = workspace(size_fn(nq, n, nlist, nprobe, d, *size_extra, k), q.device)
-    _call(f"mivq_ivf_{entry}_search", _ptr(q), nq, d, _ptr(coarse), nlist, _ptr(probe_l), nprobe, _ptr(offsets),
-          _ptr(list_codes), _ptr(list_ids), *mid, metric, k, _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids), _stream())
-    return dists, ids
+    return _search_call(f"mivq_ivf_{entry}_search", (nq, n, nlist, nprobe, d, *size_extra, k),
+                        (_ptr(q), nq, d, _ptr(coarse), nlist, _ptr(probe_l), nprobe, _ptr(offsets), _ptr(list_codes),
+                         _ptr(list_ids), *mid, metric, k), nq, k, q.device)
 
 
 def ivf_rabitq_search(q: torch.Tensor, coarse: torch.Tensor, probe_l: torch.Tensor, offsets: torch.Tensor,
@@ -1624,10 +1602,6 @@ def ivf_listpq_search(q: torch.Tensor, codebooks: torch.Tensor, coarse: torch.Te
     n, nprobe = list_codes.shape[0], probe_l.shape[1]
     if q.shape[1] != d or probe_l.shape[0] != nq or offsets.shape[0] != nlist + 1 or list_ids.shape[0] != n:
         raise ValueError("ivf_listpq_search: shape mismatch")
-    dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-    ids = torch.empty((nq, k), dtype=torch.int32, device=q.device)
-    ws = workspace(load_library().mivq_ivf_listpq_search_workspace_bytes(nq, n, nlist, nprobe, d, M, nbits, k), q.device)
-    _call("mivq_ivf_listpq_search", _ptr(q), nq, d, M, nbits, _ptr(codebooks), _ptr(coarse), nlist, _ptr(probe_l), nprobe,
-          _ptr(offsets), _ptr(list_codes), _ptr(list_ids), metric, k, _ptr(ws), ws.numel(), _ptr(dists), _ptr(ids),
-          _stream())
-    return dists, ids
+    return _search_call("mivq_ivf_listpq_search", (nq, n, nlist, nprobe, d, M, nbits, k),
+                        (_ptr(q), nq, d, M, nbits, _ptr(codebooks), _ptr(coarse), nlist, _ptr(probe_l), nprobe,
+                         _ptr(offsets), _ptr(list_codes), _ptr(list_ids), metric, k), nq, k, q.device)

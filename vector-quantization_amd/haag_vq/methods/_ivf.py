@@ -130,6 +130,25 @@ class IvfLists:
     ids: torch.Tensor         # (N,) int32 holding uint32 ids
     tau: Optional[torch.Tensor]  # (N,) f32, L2 only
 
+    def to_arrays(self) -> dict:
+        """The lists as the numpy arrays an index file holds (``tau`` only where there is one)."""
+        arrays = {name: getattr(self, name).detach().cpu().numpy() for name in ("offsets", "codes", "ids")}
+        if self.tau is not None:
+            arrays["tau"] = self.tau.detach().cpu().numpy()
+        return arrays
+
+    @classmethod
+    def from_arrays(cls, z, device) -> "IvfLists":
+        """Inverse of to_arrays (z: a mapping of numpy arrays, e.g. an open .npz); 2-byte codes are
+        the int16 rows of 16-bit SQ, every other code array is bytes."""
+        def put(a, dtype):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(device)
+
+        codes = np.asarray(z["codes"])
+        return cls(offsets=put(z["offsets"], np.int64),
+                   codes=put(codes, np.int16 if codes.dtype.itemsize == 2 else np.uint8),
+                   ids=put(z["ids"], np.int32), tau=put(z["tau"], np.float32) if "tau" in z else None)
+
 
 class _IvfEngine:
     """What the engines share: the coarse quantizer, the assignment of rows, the probe selection
@@ -252,10 +271,38 @@ class IvfRaBitQ(_IvfEngine):
                                          self.metric, k)
 
 
-class IvfCodes(_IvfEngine):
+class _IvfRowEngine(_IvfEngine):
+    """An engine whose lists are laid out once, by ``fit_lists`` (ids 0 .. N - 1), and that finds a
+    row by its id: ``pos[id]`` is the bucket position of row ``id``, ``list_of[p]`` the list of the
+    row at bucket position ``p``."""
+
+    def __init__(self, d: int, K: int, metric: int) -> None:
+        super().__init__(d, K, metric)
+        self.pos: Optional[torch.Tensor] = None
+        self.list_of: Optional[torch.Tensor] = None
+
+    def _set_lists(self, offsets: torch.Tensor, codes: torch.Tensor, order: torch.Tensor) -> None:
+        """The tail of fit_lists: codes are in bucket order, order[p] is the row at position p."""
+        self.lists = IvfLists(offsets=offsets, codes=codes, ids=order.clone(), tau=None)
+        self.ntotal = order.shape[0]
+        self._index_rows()
+
+    def _index_rows(self) -> None:
+        ids = self.lists.ids.long() & 0xFFFFFFFF
+        self.pos = torch.empty(ids.numel(), dtype=torch.int64, device=ids.device)
+        self.pos[ids] = torch.arange(ids.numel(), dtype=torch.int64, device=ids.device)
+        self.list_of = self._list_of().contiguous()
+
+    def _rows(self, rows: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(code rows, lists) of the rows with these ids."""
+        p = self.pos[rows.to(self.pos.device).long()]
+        return self.lists.codes[p].contiguous(), self.list_of[p].contiguous()
+
+
+class IvfCodes(_IvfRowEngine):
     """IVF over per-list SQ ('sq': 4 / 8 / 16 bits) or LVQ ('lvq': 1..8 bits) codes of the residuals
     (device-resident); the engine behind IvfQuantizedIndex.  ``params`` are (nlist, d) f32 tensors:
-    (lo, den) for SQ, (mu,) for LVQ; ``pos[id]`` is the bucket position of row ``id``."""
+    (lo, den) for SQ, (mu,) for LVQ."""
 
     def __init__(self, d: int, K: int, kind: str, nbits: int, metric: int = _native.METRIC_L2) -> None:
         if kind not in ("sq", "lvq"):
@@ -263,7 +310,6 @@ class IvfCodes(_IvfEngine):
         super().__init__(d, K, metric)
         self.kind, self.nbits = kind, int(nbits)
         self.params: Optional[Tuple[torch.Tensor, ...]] = None
-        self.pos: Optional[torch.Tensor] = None
 
     def _lvq_means(self, X: torch.Tensor, a: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor) -> torch.Tensor:
         """mu (K, d): the ascending-row f32 mean of every list's residuals (0 for an empty list):
@@ -307,21 +353,11 @@ class IvfCodes(_IvfEngine):
         a = self._assign(X)
         offsets, order = _native.bucket_sort(a, self.K)
         self.params = tuple(self._fit_params(X, a, offsets, order))
-        self.lists = IvfLists(offsets=offsets, codes=self._gather(self._encode(X, a), order), ids=order.clone(), tau=None)
-        self.ntotal = X.shape[0]
-        self._index_rows()
-
-    def _index_rows(self) -> None:
-        ids = self.lists.ids.long() & 0xFFFFFFFF
-        self.pos = torch.empty(ids.numel(), dtype=torch.int64, device=ids.device)
-        self.pos[ids] = torch.arange(ids.numel(), dtype=torch.int64, device=ids.device)
-        self.list_of = self._list_of().contiguous()
+        self._set_lists(offsets, self._gather(self._encode(X, a), order), order)
 
     def reconstruct(self, rows: torch.Tensor) -> torch.Tensor:
         """x^ (len(rows), d) f32 of the rows with these ids, through the decode entry points."""
-        p = self.pos[rows.to(self.pos.device).long()]
-        codes = self.lists.codes[p].contiguous()
-        a = self.list_of[p].contiguous()
+        codes, a = self._rows(rows)
         if self.kind == "sq":
             lo, den = self.params
             return _native.ivf_sq_decode(codes, self.coarse, a, lo, den, self.nbits)
@@ -347,11 +383,11 @@ def short_list_error(counts: np.ndarray, nbits: int) -> Optional[str]:
             f"{ksub} rows); use a smaller K or B")
 
 
-class IvfListPq(_IvfEngine):
+class IvfListPq(_IvfRowEngine):
     """IVF with one PQ codebook per list, fitted on the list's residuals (device-resident); the
     engine behind IvfListPqIndex.  ``codebooks`` is (K, M, ksub, dsub) f32 (zeros for an empty
-    list), the lists hold (N, M) uint8 codes in bucket order, ``pos[id]`` is the bucket position
-    of row ``id``.  ``fit_lists`` trains the K codebooks one after the other (a host loop)."""
+    list), the lists hold (N, M) uint8 codes in bucket order.  ``fit_lists`` trains the K codebooks
+    one after the other (a host loop)."""
 
     def __init__(self, d: int, K: int, M: int, nbits: int = 8, metric: int = _native.METRIC_L2, niter: int = 25,
                  seed: int = 1234) -> None:
@@ -360,8 +396,6 @@ class IvfListPq(_IvfEngine):
         super().__init__(d, K, metric)
         self.M, self.nbits, self.niter, self.seed = int(M), int(nbits), int(niter), int(seed)
         self.codebooks: Optional[torch.Tensor] = None
-        self.pos: Optional[torch.Tensor] = None
-        self.list_of: Optional[torch.Tensor] = None
 
     def fit_lists(self, X: torch.Tensor) -> None:
         """Assign every row, train each non-empty list's codebook on its residuals (ascending
@@ -388,17 +422,12 @@ class IvfListPq(_IvfEngine):
             c = _native.pq_encode(R, C, _native.pq_prepare(C, self.nbits), self.nbits)
             codes[b:e] = c if self.nbits == 8 else _native.pq_unpack(c, self.M, self.nbits)
         self.codebooks = cb
-        self.lists = IvfLists(offsets=offsets, codes=codes, ids=order.clone(), tau=None)
-        self.ntotal = n
-        self._index_rows()
-
-    _index_rows = IvfCodes._index_rows
+        self._set_lists(offsets, codes, order)
 
     def reconstruct(self, rows: torch.Tensor) -> torch.Tensor:
         """x^ (len(rows), d) f32 of the rows with these ids: pq_decode with the list's codebook + centroid."""
-        p = self.pos[rows.to(self.pos.device).long()]
-        return _native.ivf_listpq_decode(self.lists.codes[p].contiguous(), self.codebooks, self.coarse,
-                                         self.list_of[p].contiguous(), self.nbits)
+        codes, a = self._rows(rows)
+        return _native.ivf_listpq_decode(codes, self.codebooks, self.coarse, a, self.nbits)
 
     def search(self, Q: torch.Tensor, k: int, nprobe: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """(keys f32 (nq, k), ids int32 (nq, k)); L2 ascending, IP as negated inner products."""

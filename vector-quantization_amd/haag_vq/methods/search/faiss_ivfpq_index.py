@@ -24,11 +24,11 @@ import torch
 from ... import _arrays, _native
 from .._ivf import IvfLists, IvfPq
 from ..base_search_index import BaseSearchIndex
+from ._common import METRIC, results_to_host
+from ._ivf_shell import NprobeMixin
 
-_METRIC = {"l2": _native.METRIC_L2, "ip": _native.METRIC_INNER_PRODUCT}
 
-
-class FaissIvfPqIndex(BaseSearchIndex):
+class FaissIvfPqIndex(NprobeMixin, BaseSearchIndex):
     """IVF + residual PQ with ADC over the probed lists."""
 
     def __init__(self, K: int = 4096, m: int = 16, nbits: int = 8, nprobe: int = 200) -> None:
@@ -41,21 +41,13 @@ class FaissIvfPqIndex(BaseSearchIndex):
         self._N: int = 0
         self._D: int = 0
 
-    @property
-    def nprobe(self) -> int:
-        return self._nprobe
-
-    @nprobe.setter
-    def nprobe(self, v: int) -> None:
-        self._nprobe = int(v)
-
     def fit(self, X, metric: Literal["l2", "ip"] = "l2") -> None:
-        if metric not in _METRIC:
+        if metric not in METRIC:
             raise ValueError(f"unknown metric {metric!r}")
         Xd = _arrays.to_device(X)
         self._N, self._D = Xd.shape
         self._metric = metric
-        self._index = IvfPq(self._D, self._K, self._m, self._nbits, _METRIC[metric])
+        self._index = IvfPq(self._D, self._K, self._m, self._nbits, METRIC[metric])
         self._index.train(Xd)
         self._index.add(Xd)
 
@@ -66,12 +58,7 @@ class FaissIvfPqIndex(BaseSearchIndex):
 
     def _search(self, Q, k: int):
         idx = self._require()
-        d, i = idx.search(_arrays.to_device(Q), k, self._nprobe)
-        ids = _arrays.to_host(i).view(np.uint32)
-        dists = _arrays.to_host(d)
-        if self._metric == "ip":
-            dists = -dists
-        return ids, dists.astype(np.float32)
+        return results_to_host(*idx.search(_arrays.to_device(Q), k, self._nprobe), negate=self._metric == "ip")
 
     def search(self, Q, k: int) -> np.ndarray:
         return self._search(Q, k)[0]
@@ -92,17 +79,10 @@ class FaissIvfPqIndex(BaseSearchIndex):
 
     def save(self, path: str | Path) -> None:
         idx = self._require()
-        L = idx.lists
-        arrs = dict(
-            meta=np.array([self._K, self._m, self._nbits, self._nprobe, self._N, self._D, _METRIC[self._metric]],
-                          np.int64),
-            coarse=_arrays.to_host(idx.coarse), pq=_arrays.to_host(idx.pq), offsets=_arrays.to_host(L.offsets),
-            codes=_arrays.to_host(L.codes), ids=_arrays.to_host(L.ids),
-        )
-        if L.tau is not None:
-            arrs["tau"] = _arrays.to_host(L.tau)
-        with open(path, "wb") as f:
-            np.savez(f, **arrs)
+        meta = np.array([self._K, self._m, self._nbits, self._nprobe, self._N, self._D, METRIC[self._metric]], np.int64)
+        with open(path, "wb") as f:  # (the parent directory is the caller's, as in the reference)
+            np.savez(f, meta=meta, coarse=_arrays.to_host(idx.coarse), pq=_arrays.to_host(idx.pq),
+                     **idx.lists.to_arrays())
 
     def load(self, path: str | Path) -> None:
         with np.load(path, allow_pickle=False) as z:
@@ -114,9 +94,6 @@ class FaissIvfPqIndex(BaseSearchIndex):
             idx.coarse = torch.from_numpy(z["coarse"]).to(dev)
             idx.pq = torch.from_numpy(z["pq"]).to(dev)
             idx.prep = _native.pq_prepare(idx.pq, nbits)
-            idx.lists = IvfLists(offsets=torch.from_numpy(z["offsets"]).to(dev),
-                                 codes=torch.from_numpy(z["codes"]).to(dev),
-                                 ids=torch.from_numpy(z["ids"]).to(dev),
-                                 tau=torch.from_numpy(z["tau"]).to(dev) if "tau" in z.files else None)
+            idx.lists = IvfLists.from_arrays(z, dev)
             idx.ntotal = N
         self._index = idx

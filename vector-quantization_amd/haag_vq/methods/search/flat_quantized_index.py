@@ -48,8 +48,8 @@ from ..product_quantization import ProductQuantizer
 from ..rabit_quantization import RaBitQuantizer
 from ..rank_aware_quantization import RankAwareQuantizer
 from ..scalar_quantization import ScalarQuantizer
-
-_METRIC = {"l2": _native.METRIC_L2, "ip": _native.METRIC_INNER_PRODUCT}
+from ._common import MAX_K as MAX_KERNEL_K  # the wave-resident top-k of the scan kernels
+from ._common import METRIC, check_metric, empty_results, results_to_host, save_npz
 
 
 def search_codes(model: BaseQuantizer, codes, Q, k: int, metric: str = "l2",
@@ -60,7 +60,7 @@ def search_codes(model: BaseQuantizer, codes, Q, k: int, metric: str = "l2",
     returned as inner products (descending).  ``id_offset`` is added to every id (the first
     global row of a database shard, parallel/sharded.py).
     """
-    mt = _METRIC[metric]
+    mt = METRIC[metric]
     Qd = _arrays.to_device(Q)
     cd = codes if _arrays.is_tensor(codes) else torch.from_numpy(np.ascontiguousarray(codes))
     cd = cd.to(_arrays.device())
@@ -99,9 +99,6 @@ def search_codes(model: BaseQuantizer, codes, Q, k: int, metric: str = "l2",
     if mt == _native.METRIC_INNER_PRODUCT:
         d = -d
     return d, i
-
-
-MAX_KERNEL_K = 256  # the wave-resident top-k of the scan kernels
 
 
 def _search_large_k(model, cd, Qd, k: int, mt: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -233,8 +230,7 @@ class FlatQuantizedIndex(BaseSearchIndex):
         return self._quantizer
 
     def fit(self, X, metric: Literal["l2", "ip"] = "l2") -> None:
-        if metric not in _METRIC:
-            raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
+        check_metric(metric)
         Xd = _arrays.to_device(X, torch.float32)
         self._metric = metric
         self._N, self._D = Xd.shape
@@ -245,14 +241,16 @@ class FlatQuantizedIndex(BaseSearchIndex):
         ids, _ = self.search_with_scores(Q, k)
         return ids
 
+    def _search_codes(self, Q, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The device search of search_with_scores, 1 <= k <= N."""
+        return search_codes(self._quantizer, self._codes, Q, k, self._metric)
+
     def search_with_scores(self, Q, k: int) -> Tuple[np.ndarray, np.ndarray]:
         Q = np.ascontiguousarray(Q, dtype=np.float32) if not _arrays.is_tensor(Q) else Q
-        nq = Q.shape[0]
         k = min(int(k), self._N)
         if k <= 0:
-            return np.empty((nq, 0), dtype=np.uint32), np.empty((nq, 0), dtype=np.float32)
-        d, i = search_codes(self._quantizer, self._codes, Q, k, self._metric)
-        return ids_to_numpy(i), _arrays.to_host(d)
+            return empty_results(Q.shape[0], 0)
+        return results_to_host(*self._search_codes(Q, k))
 
     def memory_footprint(self) -> int:
         return int(self._codes.numel() * self._codes.element_size()) if self._codes is not None else 0
@@ -276,10 +274,7 @@ class FlatQuantizedIndex(BaseSearchIndex):
         return st
 
     def save(self, path: str | Path) -> None:
-        path = Path(path)
-        path.parent.mkdir(parents=True, exist_ok=True)
-        with open(path, "wb") as f:
-            np.savez(f, **self._state())
+        save_npz(path, **self._state())
 
     def load(self, path: str | Path) -> None:
         with np.load(Path(path), allow_pickle=False) as z:
@@ -315,16 +310,10 @@ class RankAwareFlatIndex(FlatQuantizedIndex):
             raise ValueError("RankAwareFlatIndex needs a RankAwareQuantizer")
         super().__init__(quantizer)
 
-    def search_with_scores(self, Q, k: int) -> Tuple[np.ndarray, np.ndarray]:
-        if min(int(k), self._N) > MAX_KERNEL_K:
-            return super().search_with_scores(Q, k)
-        Q = np.ascontiguousarray(Q, dtype=np.float32) if not _arrays.is_tensor(Q) else Q
-        nq = Q.shape[0]
-        k = min(int(k), self._N)
-        if k <= 0:
-            return np.empty((nq, 0), dtype=np.uint32), np.empty((nq, 0), dtype=np.float32)
-        d, i = self._quantizer.search_codes(self._codes, Q, k, self._metric)
-        return ids_to_numpy(i), _arrays.to_host(d)
+    def _search_codes(self, Q, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        if k > MAX_KERNEL_K:
+            return super()._search_codes(Q, k)
+        return self._quantizer.search_codes(self._codes, Q, k, self._metric)
 
     def load(self, path: str | Path) -> None:
         got = FlatQuantizedIndex(self._quantizer)
@@ -353,15 +342,12 @@ class ExtendedRaBitQFlatIndex(FlatQuantizedIndex):
     def search_with_scores(self, Q, k: int) -> Tuple[np.ndarray, np.ndarray]:
         if self._codes is None:
             raise RuntimeError("ExtendedRaBitQFlatIndex must be fit (or loaded) before a search")
-        if min(int(k), self._N) > MAX_KERNEL_K:
-            return super().search_with_scores(Q, k)
-        Q = np.ascontiguousarray(Q, dtype=np.float32) if not _arrays.is_tensor(Q) else Q
-        nq = Q.shape[0]
-        k = min(int(k), self._N)
-        if k <= 0:
-            return np.empty((nq, 0), dtype=np.uint32), np.empty((nq, 0), dtype=np.float32)
-        d, i = self._quantizer.search_codes(self._codes, Q, k, self._metric)
-        return ids_to_numpy(i), _arrays.to_host(d)
+        return super().search_with_scores(Q, k)
+
+    def _search_codes(self, Q, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        if k > MAX_KERNEL_K:
+            return super()._search_codes(Q, k)
+        return self._quantizer.search_codes(self._codes, Q, k, self._metric)
 
     def save(self, path: str | Path) -> None:
         if self._codes is None:

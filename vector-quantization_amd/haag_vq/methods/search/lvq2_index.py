@@ -28,10 +28,7 @@ import torch
 from ... import _arrays, _native
 from ..base_search_index import BaseSearchIndex
 from ..lvq2_quantization import TwoLevelLVQQuantizer
-from .refined_index import MAX_CANDIDATES
-
-_METRIC = {"l2": _native.METRIC_L2, "ip": _native.METRIC_INNER_PRODUCT}
-_FLT_MAX = np.finfo(np.float32).max
+from ._common import FLT_MAX, METRIC, candidate_count, check_metric, empty_results, results_to_host, save_npz
 
 
 class LVQ2Index(BaseSearchIndex):
@@ -69,8 +66,7 @@ class LVQ2Index(BaseSearchIndex):
         return self._N
 
     def fit(self, X, metric: Literal["l2", "ip"] = "l2") -> None:
-        if metric not in _METRIC:
-            raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
+        check_metric(metric)
         Xd = _arrays.to_device(X, torch.float32)
         self._quantizer.fit(Xd)
         self._codes1, self._codes2 = _native.lvq2_encode(Xd, self._quantizer._mu_device(), self.primary_bits,
@@ -80,11 +76,7 @@ class LVQ2Index(BaseSearchIndex):
 
     def candidate_count(self, k: int) -> int:
         """r, the candidates the primary scan keeps per query: min(k * refine_factor, N)."""
-        want = int(k) * self._factor
-        if want > MAX_CANDIDATES:
-            raise ValueError(f"k * refine_factor = {int(k)} * {self._factor} = {want}: the base searches keep at most "
-                             f"{MAX_CANDIDATES} results")
-        return min(want, self._N)
+        return candidate_count(k, self._factor, self._N)
 
     def search(self, Q, k: int) -> np.ndarray:
         ids, _ = self.search_with_scores(Q, k)
@@ -93,7 +85,7 @@ class LVQ2Index(BaseSearchIndex):
     def search_device(self, Qd: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """Both stages on device tensors: (keys f32 (nq, k) ascending, IP keys negated inner products;
         ids int32 (nq, k) holding uint32 ids), missing slots (+inf, 0xFFFFFFFF).  1 <= k, N >= 1."""
-        mt = _METRIC[self._metric]
+        mt = METRIC[self._metric]
         mu = self._quantizer._mu_device()
         _, cand = _native.lvq_flat_search(Qd, self._codes1, mu, self.primary_bits, self.candidate_count(k), mt)
         return _native.rerank_lvq2(Qd, cand, self._codes1, self._codes2, mu, self.primary_bits, self.residual_bits,
@@ -105,17 +97,12 @@ class LVQ2Index(BaseSearchIndex):
             raise RuntimeError("LVQ2Index must be fit (or loaded) before a search")
         nq = int(Q.shape[0])
         if int(k) <= 0 or nq == 0:
-            return np.empty((nq, max(int(k), 0)), dtype=np.uint32), np.empty((nq, max(int(k), 0)), dtype=np.float32)
-        sentinel = -_FLT_MAX if self._metric == "ip" else _FLT_MAX
+            return empty_results(nq, k)
+        sentinel = -FLT_MAX if self._metric == "ip" else FLT_MAX
         if r == 0:  # an empty database
             return np.full((nq, int(k)), _native.NO_ID, dtype=np.uint32), np.full((nq, int(k)), sentinel, dtype=np.float32)
-        d, i = self.search_device(_arrays.to_device(Q, torch.float32), int(k))
-        ids = _arrays.to_host(i).view(np.uint32)
-        dists = _arrays.to_host(d)
-        if self._metric == "ip":
-            dists = -dists
-        dists[ids == _native.NO_ID] = sentinel
-        return ids, dists
+        return results_to_host(*self.search_device(_arrays.to_device(Q, torch.float32), int(k)),
+                               negate=self._metric == "ip", sentinel=sentinel)
 
     def memory_footprint(self) -> int:
         """Both code arrays plus the mean."""
@@ -138,13 +125,10 @@ class LVQ2Index(BaseSearchIndex):
     def save(self, path: str | Path) -> None:
         if self._codes1 is None:
             raise RuntimeError("LVQ2Index.save() called before fit()")
-        path = Path(path)
-        path.parent.mkdir(parents=True, exist_ok=True)
-        with open(path, "wb") as f:
-            np.savez(f, codes1=_arrays.to_host(self._codes1), codes2=_arrays.to_host(self._codes2),
-                     mu=np.asarray(self._quantizer.mu, dtype=np.float32), primary_bits=np.array(self.primary_bits),
-                     residual_bits=np.array(self.residual_bits), metric=np.array(self._metric),
-                     refine_factor=np.array(self._factor), N=np.array(self._N), D=np.array(self._D))
+        save_npz(path, codes1=_arrays.to_host(self._codes1), codes2=_arrays.to_host(self._codes2),
+                 mu=np.asarray(self._quantizer.mu, dtype=np.float32), primary_bits=np.array(self.primary_bits),
+                 residual_bits=np.array(self.residual_bits), metric=np.array(self._metric),
+                 refine_factor=np.array(self._factor), N=np.array(self._N), D=np.array(self._D))
 
     def load(self, path: str | Path) -> None:
         path = Path(path)
@@ -157,7 +141,7 @@ class LVQ2Index(BaseSearchIndex):
             mu = np.array(z["mu"], dtype=np.float32)
             metric, factor, N, D = str(z["metric"]), int(z["refine_factor"]), int(z["N"]), int(z["D"])
         s1, s2 = _native.lvq2_code_sizes(D, b1, b2)
-        if metric not in _METRIC or factor < 1 or codes1.shape != (N, s1) or codes2.shape != (N, s2) or mu.shape != (D,):
+        if metric not in METRIC or factor < 1 or codes1.shape != (N, s1) or codes2.shape != (N, s2) or mu.shape != (D,):
             raise ValueError(f"load(): {path} is not a consistent LVQ2Index file")
         self._quantizer.mu = mu
         self._codes1 = _arrays.to_device(codes1, torch.uint8)

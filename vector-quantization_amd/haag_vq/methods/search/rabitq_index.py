@@ -25,8 +25,7 @@ import torch
 
 from ... import _arrays, _native
 from ..base_search_index import BaseSearchIndex
-
-_METRIC = {"l2": _native.METRIC_L2, "ip": _native.METRIC_INNER_PRODUCT}
+from ._common import METRIC, check_metric, empty_results, results_to_host, save_npz
 
 
 class RaBitQIndex(BaseSearchIndex):
@@ -50,15 +49,14 @@ class RaBitQIndex(BaseSearchIndex):
         return _native.rabitq_code_size(self._D)
 
     def fit(self, X, metric: Literal["l2", "ip"] = "l2") -> None:
-        if metric not in _METRIC:
-            raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
+        mt = check_metric(metric)
         Xd = _arrays.to_device(X, torch.float32)
         self._D = int(Xd.shape[1])
         self._metric = metric
         n = int(Xd.shape[0])
         center = Xd.double().sum(0) / max(n, 1) if n else torch.zeros(self._D, dtype=torch.float64, device=Xd.device)
         self._center = center.float().contiguous()
-        self._codes = _native.rabitq_encode(Xd, self._center, _METRIC[metric])
+        self._codes = _native.rabitq_encode(Xd, self._center, mt)
 
     def _require_fit(self) -> torch.Tensor:
         if self._codes is None:
@@ -73,7 +71,7 @@ class RaBitQIndex(BaseSearchIndex):
         """Device-resident search: (dists f32 (nq, k), ids int32 (nq, k) holding uint32 ids)."""
         codes = self._require_fit()
         Qd = _arrays.to_device(Q, torch.float32)
-        mt = _METRIC[self._metric]
+        mt = METRIC[self._metric]
         outs_d, outs_i = [], []
         for s in range(0, Qd.shape[0], 60000):  # query chunks (grid y of the generic kernel)
             d, i = _native.rabitq_search(codes, self._D, self._center, Qd[s:s + 60000].contiguous(), self._qb, mt, k)
@@ -86,9 +84,8 @@ class RaBitQIndex(BaseSearchIndex):
         nq = int(Q.shape[0])
         k = min(int(k), self.ntotal)
         if k <= 0:
-            return np.empty((nq, 0), dtype=np.uint32), np.empty((nq, 0), dtype=np.float32)
-        d, i = self.search_device(Q, k)
-        return _arrays.to_host(i).view(np.uint32), _arrays.to_host(d)
+            return empty_results(nq, 0)
+        return results_to_host(*self.search_device(Q, k))
 
     def memory_footprint(self) -> int:
         if self._codes is None:
@@ -113,11 +110,8 @@ class RaBitQIndex(BaseSearchIndex):
     def save(self, path: str | Path) -> None:
         if self._codes is None:
             raise RuntimeError("RaBitQIndex.save() called before fit()")
-        path = Path(path)
-        path.parent.mkdir(parents=True, exist_ok=True)
-        with open(path, "wb") as f:
-            np.savez(f, codes=_arrays.to_host(self._codes), center=_arrays.to_host(self._center),
-                     qb=np.array(self._qb), metric=np.array(self._metric), D=np.array(self._D))
+        save_npz(path, codes=_arrays.to_host(self._codes), center=_arrays.to_host(self._center),
+                 qb=np.array(self._qb), metric=np.array(self._metric), D=np.array(self._D))
 
     def load(self, path: str | Path) -> None:
         with np.load(Path(path), allow_pickle=False) as z:

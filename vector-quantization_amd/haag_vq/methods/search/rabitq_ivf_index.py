@@ -27,12 +27,11 @@ import torch
 from ... import _arrays, _native
 from .._ivf import IvfLists, IvfRaBitQ
 from ..base_search_index import BaseSearchIndex
+from ._common import MAX_K, METRIC, check_metric, empty_results, results_to_host, save_npz
+from ._ivf_shell import NprobeMixin
 
-_METRIC = {"l2": _native.METRIC_L2, "ip": _native.METRIC_INNER_PRODUCT}
-_MAX_K = 256
 
-
-class RaBitQIVFIndex(BaseSearchIndex):
+class RaBitQIVFIndex(NprobeMixin, BaseSearchIndex):
     """IVF + RaBitQ: ``nlist`` coarse cells, ``nprobe`` of them scanned per query, ``qb`` query bits."""
 
     def __init__(self, nlist: int = 256, nprobe: int = 64, qb: int = 4) -> None:
@@ -48,14 +47,6 @@ class RaBitQIVFIndex(BaseSearchIndex):
         self._metric: Literal["l2", "ip"] = "l2"
 
     @property
-    def nprobe(self) -> int:
-        return self._nprobe
-
-    @nprobe.setter
-    def nprobe(self, v: int) -> None:
-        self._nprobe = int(v)
-
-    @property
     def ntotal(self) -> int:
         return 0 if self._index is None else int(self._index.ntotal)
 
@@ -64,12 +55,11 @@ class RaBitQIVFIndex(BaseSearchIndex):
         return _native.rabitq_code_size(self._D)
 
     def fit(self, X, metric: Literal["l2", "ip"] = "l2") -> None:
-        if metric not in _METRIC:
-            raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
+        mt = check_metric(metric)
         Xd = _arrays.to_device(X, torch.float32)
         self._D = int(Xd.shape[1])
         self._metric = metric
-        index = IvfRaBitQ(self._D, self._nlist, _METRIC[metric])
+        index = IvfRaBitQ(self._D, self._nlist, mt)
         index.train(Xd)
         index.add(Xd)
         self._index = index
@@ -90,22 +80,21 @@ class RaBitQIVFIndex(BaseSearchIndex):
     def search_device(self, Q, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """Device-resident search: (dists f32 (nq, k), ids int32 (nq, k) holding uint32 ids)."""
         index = self._require_fit()
-        if k > _MAX_K:
-            raise ValueError(f"k={k}: the search supports at most k = {_MAX_K}")
+        if k > MAX_K:
+            raise ValueError(f"k={k}: the search supports at most k = {MAX_K}")
         Qd = _arrays.to_device(Q, torch.float32)
         d, i = index.search(Qd, k, self._nprobe, self._qb)
         return (-d if self._metric == "ip" else d), i
 
     def search_with_scores(self, Q, k: int) -> Tuple[np.ndarray, np.ndarray]:
         self._require_fit()
-        if int(k) > _MAX_K:
-            raise ValueError(f"k={k}: the search supports at most k = {_MAX_K}")
+        if int(k) > MAX_K:
+            raise ValueError(f"k={k}: the search supports at most k = {MAX_K}")
         nq = int(Q.shape[0])
         k = min(int(k), self.ntotal)
         if k <= 0:
-            return np.empty((nq, 0), dtype=np.uint32), np.empty((nq, 0), dtype=np.float32)
-        d, i = self.search_device(Q, k)
-        return _arrays.to_host(i).view(np.uint32), _arrays.to_host(d)
+            return empty_results(nq, 0)
+        return results_to_host(*self.search_device(Q, k))
 
     def memory_footprint(self) -> int:
         if self._index is None:
@@ -119,14 +108,9 @@ class RaBitQIVFIndex(BaseSearchIndex):
     def save(self, path: str | Path) -> None:
         if self._index is None or self._index.lists is None:
             raise RuntimeError("RaBitQIVFIndex.save() called before fit()")
-        path = Path(path)
-        path.parent.mkdir(parents=True, exist_ok=True)
-        L = self._index.lists
-        with open(path, "wb") as f:
-            np.savez(f, coarse=_arrays.to_host(self._index.coarse), offsets=_arrays.to_host(L.offsets),
-                     codes=_arrays.to_host(L.codes), ids=_arrays.to_host(L.ids), nlist=np.array(self._nlist),
-                     nprobe=np.array(self._nprobe), qb=np.array(self._qb), metric=np.array(self._metric),
-                     D=np.array(self._D))
+        save_npz(path, coarse=_arrays.to_host(self._index.coarse), **self._index.lists.to_arrays(),
+                 nlist=np.array(self._nlist), nprobe=np.array(self._nprobe), qb=np.array(self._qb),
+                 metric=np.array(self._metric), D=np.array(self._D))
 
     def load(self, path: str | Path) -> None:
         with np.load(Path(path), allow_pickle=False) as z:
@@ -135,10 +119,8 @@ class RaBitQIVFIndex(BaseSearchIndex):
             self._qb = int(z["qb"])
             self._metric = str(z["metric"])
             self._D = int(z["D"])
-            index = IvfRaBitQ(self._D, self._nlist, _METRIC[self._metric])
+            index = IvfRaBitQ(self._D, self._nlist, METRIC[self._metric])
             index.coarse = _arrays.to_device(np.array(z["coarse"]), torch.float32)
-            index.lists = IvfLists(offsets=_arrays.to_device(np.array(z["offsets"]), torch.int64),
-                                   codes=_arrays.to_device(np.array(z["codes"]), torch.uint8),
-                                   ids=_arrays.to_device(np.array(z["ids"]), torch.int32), tau=None)
+            index.lists = IvfLists.from_arrays(z, _arrays.device())
             index.ntotal = int(index.lists.ids.shape[0])
         self._index = index

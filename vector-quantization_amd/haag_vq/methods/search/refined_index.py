@@ -34,10 +34,8 @@ from ..base_quantizer import BaseQuantizer
 from ..base_search_index import BaseSearchIndex
 from ..lvq_quantization import LVQQuantizer
 from ..scalar_quantization import ScalarQuantizer
-
-_METRIC = {"l2": _native.METRIC_L2, "ip": _native.METRIC_INNER_PRODUCT}
-MAX_CANDIDATES = 256  # what a base search returns at most (the wave-resident top-k of the kernels)
-_FLT_MAX = np.finfo(np.float32).max
+from ._common import MAX_CANDIDATES  # noqa: F401  (what a base search returns at most; importable from here)
+from ._common import FLT_MAX, METRIC, candidate_count, check_metric, empty_results, results_to_host, save_npz
 
 
 def _kind_of(refine: Optional[BaseQuantizer]) -> Tuple[str, int]:
@@ -84,8 +82,7 @@ class RefinedIndex(BaseSearchIndex):
         return self._N
 
     def fit(self, X, metric: Literal["l2", "ip"] = "l2") -> None:
-        if metric not in _METRIC:
-            raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
+        check_metric(metric)
         self._base.fit(X, metric)
         Xd = _arrays.to_device(X, torch.float32)
         if self._kind == "f32":
@@ -102,11 +99,7 @@ class RefinedIndex(BaseSearchIndex):
 
     def candidate_count(self, k: int) -> int:
         """r, the candidates asked of the base index per query: min(k * refine_factor, N)."""
-        want = int(k) * self._factor
-        if want > MAX_CANDIDATES:
-            raise ValueError(f"k * refine_factor = {int(k)} * {self._factor} = {want}: the base searches keep at most "
-                             f"{MAX_CANDIDATES} results")
-        return min(want, self._N)
+        return candidate_count(k, self._factor, self._N)
 
     def search(self, Q, k: int) -> np.ndarray:
         ids, _ = self.search_with_scores(Q, k)
@@ -118,8 +111,8 @@ class RefinedIndex(BaseSearchIndex):
             raise RuntimeError("RefinedIndex must be fit (or loaded) before a search")
         nq = int(Q.shape[0])
         if int(k) <= 0 or nq == 0:
-            return np.empty((nq, max(int(k), 0)), dtype=np.uint32), np.empty((nq, max(int(k), 0)), dtype=np.float32)
-        sentinel = -_FLT_MAX if self._metric == "ip" else _FLT_MAX
+            return empty_results(nq, k)
+        sentinel = -FLT_MAX if self._metric == "ip" else FLT_MAX
         cand = self._base.search(Q, r) if r > 0 else np.empty((nq, 0), dtype=np.uint32)
         if _arrays.is_tensor(cand):
             cand = _arrays.to_host(cand)
@@ -127,13 +120,8 @@ class RefinedIndex(BaseSearchIndex):
         if cand.shape[1] == 0:  # an empty database
             return np.full((nq, int(k)), _native.NO_ID, dtype=np.uint32), np.full((nq, int(k)), sentinel, dtype=np.float32)
         d, i = _native.rerank(self._kind, _arrays.to_device(Q, torch.float32), _arrays.to_device(cand, torch.int32),
-                              self._store, self._params, self._bits, int(k), _METRIC[self._metric])
-        ids = _arrays.to_host(i).view(np.uint32)
-        dists = _arrays.to_host(d)
-        if self._metric == "ip":
-            dists = -dists
-        dists[ids == _native.NO_ID] = sentinel
-        return ids, dists
+                              self._store, self._params, self._bits, int(k), METRIC[self._metric])
+        return results_to_host(d, i, negate=self._metric == "ip", sentinel=sentinel)
 
     def _store_bytes(self) -> int:
         if self._store is None:
@@ -153,12 +141,9 @@ class RefinedIndex(BaseSearchIndex):
         if self._store is None:
             raise RuntimeError("RefinedIndex.save() called before fit()")
         path = Path(path)
-        path.parent.mkdir(parents=True, exist_ok=True)
-        arrays = {f"param{i}": _arrays.to_host(t) for i, t in enumerate(self._params)}
-        with open(path, "wb") as f:
-            np.savez(f, store=_arrays.to_host(self._store), kind=np.array(self._kind), bits=np.array(self._bits),
-                     metric=np.array(self._metric), refine_factor=np.array(self._factor), N=np.array(self._N),
-                     D=np.array(self._D), **arrays)
+        save_npz(path, store=_arrays.to_host(self._store), kind=np.array(self._kind), bits=np.array(self._bits),
+                 metric=np.array(self._metric), refine_factor=np.array(self._factor), N=np.array(self._N),
+                 D=np.array(self._D), **{f"param{i}": _arrays.to_host(t) for i, t in enumerate(self._params)})
         self._base.save(_base_path(path))
 
     def load(self, path: str | Path) -> None:
@@ -172,7 +157,7 @@ class RefinedIndex(BaseSearchIndex):
             store = np.array(z["store"])
             params = [np.array(z[f"param{i}"], dtype=np.float32) for i in range(nparams)]
             metric, factor, N, D = str(z["metric"]), int(z["refine_factor"]), int(z["N"]), int(z["D"])
-        if metric not in _METRIC or factor < 1 or store.ndim != 2 or store.shape[0] != N or any(p.shape != (D,) for p in params):
+        if metric not in METRIC or factor < 1 or store.ndim != 2 or store.shape[0] != N or any(p.shape != (D,) for p in params):
             raise ValueError(f"load(): {path} is not a consistent RefinedIndex file")
         self._base.load(_base_path(path))
         dt = torch.float32 if kind == "f32" else torch.int16 if store.dtype.itemsize == 2 else torch.uint8

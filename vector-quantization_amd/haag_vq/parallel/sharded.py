@@ -173,10 +173,9 @@ class ShardedFlatIndex(BaseSearchIndex):
         return self._offset
 
     def fit(self, X, metric: Literal["l2", "ip"] = "l2", train=None) -> None:
-        from ..methods.search.flat_quantized_index import _METRIC
+        from ..methods.search._common import check_metric
 
-        if metric not in _METRIC:
-            raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
+        check_metric(metric)
         rank, _ = _world()
         Xd = _arrays.to_device(X, torch.float32)
         self._metric = metric
