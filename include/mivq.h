@@ -8,6 +8,10 @@
  *   - Ownership: every buffer is caller-allocated DEVICE memory (e.g. a torch tensor's
  *     data_ptr()).  The library never allocates persistent memory; kernels that need
  *     scratch take an explicit workspace (size from the matching *_workspace_bytes()).
+ *     A call writes its outputs and its workspace and nothing else, and does not depend on
+ *     what the workspace or an output held before; a workspace that is null or smaller
+ *     than the size query's is MIVQ_ERR_WORKSPACE, reported before any launch (DESIGN.md,
+ *     "Buffer contract").
  *   - Errors: 0 on success, a negative MIVQ_ERR_* code otherwise; the message is kept in
  *     a thread-local buffer readable with mivq_last_error().  The Python host raises the
  *     same exception types the reference raises (AssertionError / ValueError /
@@ -343,8 +347,8 @@ int mivq_rankaware_flat_search(const float* qy, int64_t nq, const uint8_t* codes
  * A row that is not ascending or holds non-finite values gives unspecified levels but no access
  * outside the row, its slot and its levels.
  * n < 0, d < 0, an unknown method, a width outside 0..8, an lv_off that does not match the widths,
- * a null pointer or fewer than 2^max width draws return MIVQ_ERR_INVALID, a workspace below one
- * slot of the widest dimension MIVQ_ERR_WORKSPACE and n above 2^26 MIVQ_ERR_UNSUPPORTED, all
+ * a null pointer or fewer than 2^max width draws return MIVQ_ERR_INVALID, a null workspace or one below
+ * one slot of the widest dimension MIVQ_ERR_WORKSPACE and n above 2^26 MIVQ_ERR_UNSUPPORTED, all
  * before any launch; n == 0 or d == 0 returns MIVQ_OK without one.  The size query returns 0 for
  * arguments fit would refuse. */
 #define MIVQ_CB1D_EXACT 0

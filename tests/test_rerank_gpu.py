@@ -181,7 +181,10 @@ def test_many_queries(dev):
 
 
 def test_workspace_size(dev, listdb):
-    """The size query's bytes are enough (every call above allocates exactly them); one byte less is refused."""
+    """A workspace of the size query's bytes is accepted and gives the rule's result; one byte less
+    is refused.  This does not show that the call stays inside those bytes: the torch blocks here
+    and in the wrapper's calls above are padded by the allocator.  tests/test_bounds_search_gpu.py
+    runs the entry point in a guarded arena with exactly the reported bytes."""
     from haag_vq import _native
 
     lib = _native.load_library()

@@ -609,10 +609,10 @@ extern "C" int mivq_codebook1d_fit(const float* cols, int64_t n, int32_t d, cons
     if (maxw == 0) return MIVQ_OK;
     MIVQ_REQUIRE(n <= kCbMaxN, MIVQ_ERR_UNSUPPORTED, "codebook1d_fit: n=%lld above %lld", (long long)n,
                  (long long)kCbMaxN);
-    MIVQ_REQUIRE(workspace_bytes >= cb_slot(n, maxw, method).total, MIVQ_ERR_WORKSPACE,
+    MIVQ_REQUIRE(workspace && workspace_bytes >= cb_slot(n, maxw, method).total, MIVQ_ERR_WORKSPACE,
                  "codebook1d_fit: workspace %zu < %zu bytes for one dimension of %d bits", workspace_bytes,
                  cb_slot(n, maxw, method).total, maxw);
-    MIVQ_REQUIRE(cols && levels && sse && workspace, MIVQ_ERR_INVALID, "codebook1d_fit: null pointer");
+    MIVQ_REQUIRE(cols && levels && sse, MIVQ_ERR_INVALID, "codebook1d_fit: null pointer");
     MIVQ_REQUIRE(method != MIVQ_CB1D_LLOYD || (draws && ndraws >= (1 << maxw)), MIVQ_ERR_INVALID,
                  "codebook1d_fit: lloyd needs at least %d draws, got %d", 1 << maxw, ndraws);
 

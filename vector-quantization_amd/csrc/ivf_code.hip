@@ -367,7 +367,7 @@ extern "C" int mivq_ivf_sq_search(const float* q, int64_t nq, int32_t d, const f
                                   uint32_t* ids, void* stream) {
     const int rc = ic_search_prologue("ivf_sq_search", nq, d, nlist, nprobe, sq_bits_ok(nbits), nbits, false, metric, k);
     if (rc != MIVQ_OK || nq == 0) return rc;
-    MIVQ_REQUIRE(q && coarse && probe_l && offsets && list_codes && list_ids && lo && den && dists && ids && workspace,
+    MIVQ_REQUIRE(q && coarse && probe_l && offsets && list_codes && list_ids && lo && den && dists && ids,
                  MIVQ_ERR_INVALID, "ivf_sq_search: null pointer");
     if (const int ra = sq16_aligned("ivf_sq_search", nbits, list_codes)) return ra;
     return with_sq_bits(nbits, [&](auto F) {
@@ -384,7 +384,7 @@ extern "C" int mivq_ivf_lvq_search(const float* q, int64_t nq, int32_t d, const 
                                    uint32_t* ids, void* stream) {
     const int rc = ic_search_prologue("ivf_lvq_search", nq, d, nlist, nprobe, lvq_bits_ok(nbits), nbits, true, metric, k);
     if (rc != MIVQ_OK || nq == 0) return rc;
-    MIVQ_REQUIRE(q && coarse && probe_l && offsets && list_codes && list_ids && mu && dists && ids && workspace,
+    MIVQ_REQUIRE(q && coarse && probe_l && offsets && list_codes && list_ids && mu && dists && ids,
                  MIVQ_ERR_INVALID, "ivf_lvq_search: null pointer");
     return with_lvq_bits(nbits, [&](auto F) {
         return ivf_code_search<decltype(F)::value>("ivf_lvq_search", q, nq, d, coarse, nlist, probe_l, nprobe, offsets,

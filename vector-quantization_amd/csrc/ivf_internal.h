@@ -240,8 +240,8 @@ template <int PPI, class Prep, class Scan>
 int ivf_probed_search(const char* name, const IvfLayout& L, int64_t nq, int nlist, int nprobe, int k,
                       const int64_t* offsets, const uint8_t* list_codes, const uint32_t* list_ids, void* workspace,
                       size_t workspace_bytes, float* dists, uint32_t* ids, void* stream, Prep&& prep, Scan&& scan) {
-    MIVQ_REQUIRE(workspace_bytes >= L.total, MIVQ_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", name, workspace_bytes,
-                 L.total);
+    MIVQ_REQUIRE(workspace && workspace_bytes >= L.total, MIVQ_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", name,
+                 workspace_bytes, L.total);
     auto fail = [&](const char* step, hipError_t e) {
         return set_error(MIVQ_ERR_HIP, "%s (%s): %s", name, step, hipGetErrorString(e));
     };

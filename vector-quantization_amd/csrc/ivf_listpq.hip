@@ -394,7 +394,7 @@ extern "C" int mivq_ivf_listpq_search(const float* q, int64_t nq, int32_t d, int
     MIVQ_REQUIRE(M > 0 && d % M == 0, MIVQ_ERR_INVALID, "%s: d=%d must be divisible by M=%d", name, d, M);
     MIVQ_REQUIRE(nbits >= 1 && nbits <= 8, MIVQ_ERR_INVALID, "%s: nbits=%d not in [1, 8]", name, nbits);
     if (nq == 0) return MIVQ_OK;
-    MIVQ_REQUIRE(q && codebooks && coarse && probe_l && offsets && list_codes && list_ids && dists && ids && workspace,
+    MIVQ_REQUIRE(q && codebooks && coarse && probe_l && offsets && list_codes && list_ids && dists && ids,
                  MIVQ_ERR_INVALID, "%s: null pointer", name);
     hipStream_t st = as_stream(stream);
     return with_query_block<kLpMaxQB>(ivf_pairs_per_item(kLpMaxQB, nq, nlist, nprobe), [&](auto QB) {

@@ -299,7 +299,7 @@ extern "C" int mivq_ivf_rabitq_search(const float* q, int64_t nq, int32_t d, con
     if (rc != MIVQ_OK) return rc;
     MIVQ_REQUIRE(qb >= 0 && qb <= 8, MIVQ_ERR_UNSUPPORTED, "ivf_rabitq_search: qb=%d not in [0, 8]", qb);
     if (nq == 0) return MIVQ_OK;
-    MIVQ_REQUIRE(q && coarse && probe_l && offsets && list_codes && list_ids && dists && ids && workspace,
+    MIVQ_REQUIRE(q && coarse && probe_l && offsets && list_codes && list_ids && dists && ids,
                  MIVQ_ERR_INVALID, "ivf_rabitq_search: null pointer");
     // the MFMA scan: d % 32 == 0 (whole k-steps, 4-B aligned code rows), qb >= 1, the 32 int8 rows in LDS
     const bool mfma = qb > 0 && d % 32 == 0 && reinterpret_cast<uintptr_t>(list_codes) % 4 == 0 &&

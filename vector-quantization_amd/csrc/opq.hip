@@ -204,6 +204,8 @@ __global__ __launch_bounds__(1024) void opq_absmax_kernel(const float* __restric
         hdr[0] = s;
         hdr[1] = 1.0f / s;
     }
+    // the rest of the 256-byte header: zero, so that equal matrices give byte-equal prep buffers
+    if (threadIdx.x >= 2 && threadIdx.x < 64) hdr[threadIdx.x] = 0.0f;
 }
 
 // B image: bimg[plane][j][k] = split(s_b * op(A)[k][j]), plane 0 = hi, 1 = lo; op(A)[k][j] =

@@ -580,7 +580,7 @@ extern "C" int mivq_rabitq_search(const uint8_t* codes, int64_t n, int32_t d, co
     MIVQ_REQUIRE(metric == MIVQ_METRIC_L2 || metric == MIVQ_METRIC_INNER_PRODUCT, MIVQ_ERR_UNSUPPORTED,
                  "rabitq_search: metric %d", metric);
     if (nq == 0) return MIVQ_OK;
-    MIVQ_REQUIRE(q && dists && ids && workspace, MIVQ_ERR_INVALID, "rabitq_search: null pointer");
+    MIVQ_REQUIRE(q && dists && ids, MIVQ_ERR_INVALID, "rabitq_search: null pointer");
     MIVQ_REQUIRE(n == 0 || codes, MIVQ_ERR_INVALID, "rabitq_search: null codes");
     const bool mfma = qb > 0 && (d % 32) == 0 && (reinterpret_cast<uintptr_t>(codes) % 4) == 0;
     // the generic estimator's grid is (code blocks, nq) and grid.y is limited to 65535
@@ -588,7 +588,7 @@ extern "C" int mivq_rabitq_search(const uint8_t* codes, int64_t n, int32_t d, co
                  "rabitq_search: nq=%lld > 65535 queries per call (qb = 0, d %% 32 != 0 or unaligned codes)",
                  (long long)nq);
     const RqLayout L = rq_layout(nq, n, d, k);
-    MIVQ_REQUIRE(workspace_bytes >= L.total, MIVQ_ERR_INVALID, "rabitq_search: workspace %zu < %zu bytes",
+    MIVQ_REQUIRE(workspace && workspace_bytes >= L.total, MIVQ_ERR_WORKSPACE, "rabitq_search: workspace %zu < %zu bytes",
                  workspace_bytes, L.total);
     hipStream_t st = as_stream(stream);
     unsigned char* p = static_cast<unsigned char*>(workspace);
