@@ -13,6 +13,9 @@ from pathlib import Path
 from typing import Any, Dict, Optional, Union
 
 import numpy as np
+import torch
+
+from .. import _arrays, _native
 
 
 class BaseQuantizer(ABC):
@@ -29,6 +32,23 @@ class BaseQuantizer(ABC):
     @abstractmethod
     def decompress(self, codes: np.ndarray) -> np.ndarray:
         """Reconstruct approximations (N, D) from codes."""
+
+    # ---- what the search indices ask of a quantizer; not in the reference's interface, and the
+    # defaults keep a foreign subclass working
+    qtype: Optional[str] = None      # the "qtype" member of the saved state
+    code_kind: Optional[str] = None  # "sq" / "lvq": a format the re-rank and IVF kernels read, whose
+    #                                  per-dimension f32 device tensors code_params() returns
+
+    def to_state(self) -> dict:
+        """The fitted quantizer as plain numpy arrays; the classmethod ``from_state`` inverts it."""
+        raise ValueError(f"save(): unsupported quantizer {type(self).__name__}")
+
+    def flat_keys(self, codes_dev, Q_dev, k: int, mt: int, id_offset: int = 0):
+        """The exact ranking of device queries over device codes, k <= 256: (keys f32, ids int32),
+        kernel keys ascending (IP: negated inner products).  Here decode + ``mivq_flat_search``;
+        a quantizer whose codes can be ranked as they are overrides it."""
+        xh = _arrays.to_device(self.decompress(codes_dev), torch.float32)
+        return _native.flat_search(Q_dev, xh, k, mt, id_offset=id_offset)
 
     def save_codebooks(
         self,

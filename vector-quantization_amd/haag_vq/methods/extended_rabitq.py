@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .. import _arrays, _native
+from ._rotated import RotatedSearch
 from .base_quantizer import BaseQuantizer
 
 
@@ -46,7 +47,9 @@ def _lloyd_1d_normal(num_levels: int, seed: int, n_samples: int = 200_000, max_i
     return levels.astype(np.float64)
 
 
-class ExtendedRaBitQuantizer(BaseQuantizer):
+class ExtendedRaBitQuantizer(RotatedSearch, BaseQuantizer):
+    qtype = "extrabitq"
+
     def __init__(self, num_bits: int = 4, seed: int = 0):
         if num_bits < 1 or num_bits > 8:
             raise ValueError("num_bits must be in [1, 8]")
@@ -119,45 +122,29 @@ class ExtendedRaBitQuantizer(BaseQuantizer):
                                                                 c, P, lv, self.num_bits))
         return out
 
-    def _queries(self, Q) -> torch.Tensor:
+    # RotatedSearch with centre c and rotation P (orthogonal, x_hat = (o_hat P^T) nrm + c, so
+    # y_hat = o_hat nrm); the bit fields are scanned against the shared level table and nrm / t
+    def _fitted(self) -> bool:
+        return self.P is not None
+
+    def _scan(self, Qy, codes, k: int, mt: int, id_offset: int):
+        return _native.extrabitq_flat_search(Qy, codes, self._state()[2], self.num_bits, k, mt, id_offset=id_offset)
+
+    def to_state(self) -> dict:
         if self.P is None:
-            raise RuntimeError("Quantizer must be fit before a search.")
-        if not _arrays.is_tensor(Q):
-            Q = np.ascontiguousarray(Q)
-        if len(Q.shape) != 2 or Q.shape[1] != self.D:
-            raise ValueError(f"queries must be (nq, {self.D}), got shape {tuple(Q.shape)}")
-        dt = torch.float64 if str(Q.dtype).endswith("float64") else torch.float32
-        return _arrays.to_device(Q, dt).contiguous()
+            raise ValueError("save(): the ExtendedRaBitQuantizer is not fitted")
+        return dict(qtype=np.array(self.qtype), num_bits=np.array(self.num_bits), seed=np.array(self.seed),
+                    D=np.array(self.D), c=np.asarray(self.c, dtype=np.float64),
+                    P=np.ascontiguousarray(self.P, dtype=np.float64), levels=np.asarray(self.levels, dtype=np.float64))
 
-    def rotate_queries(self, Q, metric: str = "l2") -> torch.Tensor:
-        """The queries in the rotated domain, (nq, D) f32 on the device: ``(Q - c) P`` for L2 and
-        ``Q P`` for IP, computed in fp64 and rounded once."""
-        if metric not in ("l2", "ip"):
-            raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
-        Qd = self._queries(Q)
-        c, P, _ = self._state()
-        return _native.gemm_f64(_native.rankaware_center(Qd, c if metric == "l2" else torch.zeros_like(c)), P,
-                                False).to(torch.float32)
-
-    def search_codes(self, codes, Q, k: int, metric: str = "l2", id_offset: int = 0):
-        """Top-k of Q over ``codes`` without decoding them (``mivq_extrabitq_flat_search``, k <= 256).
-
-        P is orthogonal and x_hat = (o_hat P^T) nrm + c, so ||q - x_hat||^2 = ||(q - c) P - y_hat||^2
-        and <q, x_hat> = <q P, y_hat> + <q, c> with y_hat = o_hat nrm: only the queries are rotated,
-        the codes are scanned as bit fields against the shared level table.  Returns device tensors
-        (dists f32 (nq, k), ids int32 (nq, k) holding uint32 ids): squared L2 distances ascending,
-        or inner products descending (the kernel's key negated plus f32(<q, c>), one f32 add per
-        query)."""
-        Qy = self.rotate_queries(Q, metric)
-        c, _, lv = self._state()
-        cd = codes if _arrays.is_tensor(codes) else torch.from_numpy(np.ascontiguousarray(codes, dtype=np.uint8))
-        cd = _arrays.to_device(cd, torch.uint8).contiguous()
-        mt = _native.METRIC_L2 if metric == "l2" else _native.METRIC_INNER_PRODUCT
-        d, i = _native.extrabitq_flat_search(Qy, cd, lv, self.num_bits, int(k), mt, id_offset=int(id_offset))
-        if metric == "ip":
-            qc = (self._queries(Q).to(torch.float64) @ c).to(torch.float32)
-            d = -d + qc[:, None]
-        return d, i
+    @classmethod
+    def from_state(cls, z) -> "ExtendedRaBitQuantizer":
+        q = cls(num_bits=int(z["num_bits"]), seed=int(z["seed"]))
+        q.D = int(z["D"])
+        q.c, q.P, q.levels = (np.array(z[nm], dtype=np.float64) for nm in ("c", "P", "levels"))
+        if q.c.shape != (q.D,) or q.P.shape != (q.D, q.D) or q.levels.shape != (2 ** q.num_bits,):
+            raise ValueError("load(): inconsistent Extended RaBitQ quantizer state")
+        return q
 
     def get_compression_ratio(self, X) -> float:
         return float(int(X.shape[1]) * 4 / self.code_size)

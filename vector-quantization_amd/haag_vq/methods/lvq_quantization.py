@@ -21,6 +21,9 @@ from .base_quantizer import BaseQuantizer
 
 
 class LVQQuantizer(BaseQuantizer):
+    qtype = "lvq"
+    code_kind = "lvq"
+
     def __init__(self, num_bits: int = 8) -> None:
         if not (1 <= num_bits <= 8):
             raise ValueError(f"num_bits must be in [1, 8], got {num_bits}")
@@ -73,6 +76,24 @@ class LVQQuantizer(BaseQuantizer):
         for s, e in _arrays.row_chunks(n, d * 4):
             out[s:e] = _arrays.to_host(_native.lvq_decode(_arrays.to_device(codes[s:e], torch.uint8), mu, self.num_bits))
         return out
+
+    def flat_keys(self, codes_dev, Q_dev, k: int, mt: int, id_offset: int = 0):  # = decode + search, bit for bit
+        if self._mu is None:
+            return super().flat_keys(codes_dev, Q_dev, k, mt, id_offset)
+        return _native.lvq_flat_search(Q_dev, _arrays.to_device(codes_dev, torch.uint8).contiguous(), self._mu_device(),
+                                       self.num_bits, k, mt, id_offset=id_offset)
+
+    def code_params(self) -> tuple:  # (mu,)
+        return (self._mu_device(),)
+
+    def to_state(self) -> dict:
+        return dict(qtype=np.array(self.qtype), num_bits=np.array(self.num_bits), mu=np.asarray(self.mu, dtype=np.float32))
+
+    @classmethod
+    def from_state(cls, z) -> "LVQQuantizer":
+        q = cls(num_bits=int(z["num_bits"]))
+        q.mu = np.array(z["mu"])
+        return q
 
     def get_compression_ratio(self, X) -> float:
         """Original float32 bytes per vector over the code bytes per vector."""

@@ -137,6 +137,8 @@ def polar_factor(G: torch.Tensor, tol: float = 1e-13, max_iter: int = 60, info: 
 
 
 class OptimizedProductQuantizer(BaseQuantizer):
+    qtype = "opq"
+
     def __init__(self, M: int, B: int = 8):
         """OPQ (Ge et al., TPAMI 2013).  M sub-quantizers of 2**B centroids."""
         self.M = M
@@ -223,6 +225,22 @@ class OptimizedProductQuantizer(BaseQuantizer):
     def inner(self) -> ProductQuantizer:
         self._require("inner")
         return self._inner
+
+    def flat_keys(self, codes_dev, Q_dev, k: int, mt: int, id_offset: int = 0):
+        """ADC of the rotated queries: the orthonormal rotation keeps distances and inner products."""
+        return self.inner.flat_keys(codes_dev, self.opq.apply(Q_dev), k, mt, id_offset)
+
+    def to_state(self) -> dict:
+        return dict(qtype=np.array(self.qtype), M=np.array(self.M), B=np.array(self.B),
+                    A=_arrays.to_host(self.opq.A_device), centroids=_arrays.to_host(self.inner._C))
+
+    @classmethod
+    def from_state(cls, z) -> "OptimizedProductQuantizer":
+        q = cls(M=int(z["M"]), B=int(z["B"]))
+        q.opq = OPQHandle(_arrays.to_device(z["A"]))
+        q._inner = ProductQuantizer.from_state(z)
+        q.pq = q._inner.pq
+        return q
 
     def get_compression_ratio(self, X) -> float:
         """D*4 / ceil(M*B/8) — optimized_product_quantization.py:36-46."""

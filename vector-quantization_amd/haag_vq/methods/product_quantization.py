@@ -69,6 +69,8 @@ class PQHandle:
 
 
 class ProductQuantizer(BaseQuantizer):
+    qtype = "pq"
+
     def __init__(
         self,
         M: Optional[int] = None,
@@ -169,6 +171,24 @@ class ProductQuantizer(BaseQuantizer):
             rec = _native.pq_decode(_arrays.to_device(codes[s:e], torch.uint8), self._C, self.B)
             out[s:e] = _arrays.to_host(rec)
         return out
+
+    def flat_keys(self, codes_dev, Q_dev, k: int, mt: int, id_offset: int = 0):
+        """ADC: per-query lookup tables (``mivq_adc_lut``) summed over the codes (``mivq_adc_search``).
+        sum_m ||q_m - c_{m,code_m}||^2 equals ||q - x_hat||^2, so the ranking is that of decode +
+        search up to fp32 rounding on near-ties, without materialising x_hat."""
+        cd = codes_dev.to(torch.uint8).contiguous()
+        u8 = cd if self.B == 8 else _native.pq_unpack(cd, self.M, self.B)
+        lut = _native.adc_lut(Q_dev, self.centroids_device, self.B, mt)
+        return _native.adc_search(lut, u8, k, self.B, id_offset=id_offset)
+
+    def to_state(self) -> dict:
+        return dict(qtype=np.array(self.qtype), M=np.array(self.M), B=np.array(self.B), centroids=_arrays.to_host(self._C))
+
+    @classmethod
+    def from_state(cls, z) -> "ProductQuantizer":
+        q = cls(M=int(z["M"]), B=int(z["B"]))
+        q.set_codebooks(z["centroids"])
+        return q
 
     def get_compression_ratio(self, X) -> float:
         """Original bytes (float32) over code bytes — product_quantization.py:88-99."""

@@ -35,6 +35,8 @@ class RaBitQHandle:
 
 
 class RaBitQuantizer(BaseQuantizer):
+    qtype = "rabitq"
+
     def __init__(self, metric_type: MetricType = MetricType.L2):
         """RaBitQ (Gao & Long, SIGMOD 2024), 1 bit per dimension."""
         self.metric_type = metric_type
@@ -73,6 +75,21 @@ class RaBitQuantizer(BaseQuantizer):
         for s, e in _arrays.row_chunks(n, d * 4):
             out[s:e] = _arrays.to_host(_native.rabitq_decode(_arrays.to_device(compressed[s:e], torch.uint8), d, None))
         return out
+
+    def flat_keys(self, codes_dev, Q_dev, k: int, mt: int, id_offset: int = 0):  # = decode + search, bit for bit
+        if self.rabitq is None:
+            return super().flat_keys(codes_dev, Q_dev, k, mt, id_offset)
+        return _native.rabitq_flat_search(Q_dev, _arrays.to_device(codes_dev, torch.uint8).contiguous(), self.rabitq.d,
+                                          None, k, mt, id_offset=id_offset)
+
+    def to_state(self) -> dict:
+        return dict(qtype=np.array(self.qtype), metric_type=np.array(int(self.metric_type)), d=np.array(self.rabitq.d))
+
+    @classmethod
+    def from_state(cls, z) -> "RaBitQuantizer":
+        q = cls(metric_type=MetricType(int(z["metric_type"])))
+        q.fit(np.empty((0, int(z["d"])), dtype=np.float32))
+        return q
 
     def get_compression_ratio(self, X):
         D = int(X.shape[1])

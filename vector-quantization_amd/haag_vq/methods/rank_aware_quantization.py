@@ -42,6 +42,7 @@ import numpy as np
 import torch
 
 from .. import _arrays, _native
+from ._rotated import RotatedSearch
 from .base_quantizer import BaseQuantizer
 from .ffd_packing import ffd_layout
 
@@ -105,7 +106,9 @@ def allocate_bits(var: np.ndarray, Dg: np.ndarray, avg_bits: float, alpha: float
     return bits
 
 
-class RankAwareQuantizer(BaseQuantizer):
+class RankAwareQuantizer(RotatedSearch, BaseQuantizer):
+    qtype = "rankaware"
+
     def __init__(self, avg_bits: float, alpha: float = 1.0, max_bits: int = 8, seed: int = 0,
                  packing: str = "dense", codebook: str = "gaussian", codebook_engine: str = "saq"):
         if max_bits < 1 or max_bits > 8:
@@ -290,45 +293,49 @@ class RankAwareQuantizer(BaseQuantizer):
         return out
 
     # --------------------------------------------------------------- search
-    def _queries(self, Q) -> torch.Tensor:
+    # RotatedSearch with centre mu and rotation V (orthogonal, x_hat = y_hat V^T + mu); the packed
+    # fields are scanned against the per-dimension level tables
+    def _fitted(self) -> bool:
+        return self.V is not None
+
+    def _scan(self, Qy, codes, k: int, mt: int, id_offset: int):
+        return _native.rankaware_flat_search(Qy, codes, self._state(), k, mt, id_offset=id_offset)
+
+    def to_state(self) -> dict:
         if self.V is None:
-            raise RuntimeError("Quantizer must be fit before a search.")
-        if not _arrays.is_tensor(Q):
-            Q = np.ascontiguousarray(Q)
-        if len(Q.shape) != 2 or Q.shape[1] != self.D:
-            raise ValueError(f"queries must be (nq, {self.D}), got shape {tuple(Q.shape)}")
-        dt = torch.float64 if str(Q.dtype).endswith("float64") else torch.float32
-        return _arrays.to_device(Q, dt).contiguous()
+            raise ValueError("save(): the RankAwareQuantizer is not fitted")
+        st = dict(qtype=np.array(self.qtype), avg_bits=np.array(self.avg_bits), alpha=np.array(self.alpha),
+                  max_bits=np.array(self.max_bits), seed=np.array(self.seed), packing=np.array(self.packing),
+                  mu=np.asarray(self.mu, dtype=np.float64), V=np.ascontiguousarray(self.V, dtype=np.float64),
+                  var=np.asarray(self.var, dtype=np.float64), bits=np.asarray(self.bits, dtype=np.int64),
+                  cb=np.concatenate(self.cb).astype(np.float64),
+                  levels=np.concatenate(self._levels).astype(np.float64), Dg=np.asarray(self._Dg, dtype=np.float64))
+        # written only when not the defaults: a gaussian quantizer's file keeps its bytes
+        if self.codebook != "gaussian":
+            st["codebook"] = np.array(self.codebook)
+        if self.codebook_engine != "saq":
+            st["codebook_engine"] = np.array(self.codebook_engine)
+        return st
 
-    def rotate_queries(self, Q, metric: str = "l2") -> torch.Tensor:
-        """The queries in the rotated domain, (nq, D) f32 on the device: ``(Q - mu) V`` for L2 and
-        ``Q V`` for IP, computed in fp64 and rounded once."""
-        if metric not in ("l2", "ip"):
-            raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
-        Qd = self._queries(Q)
-        st = self._state()
-        mu = st.mu if metric == "l2" else torch.zeros_like(st.mu)
-        return _native.gemm_f64(_native.rankaware_center(Qd, mu), st.V, False).to(torch.float32)
-
-    def search_codes(self, codes, Q, k: int, metric: str = "l2", id_offset: int = 0):
-        """Top-k of Q over ``codes`` without decoding them (``mivq_rankaware_flat_search``, k <= 256).
-
-        V is orthogonal and x_hat = y_hat V^T + mu, so ||q - x_hat||^2 = ||(q - mu) V - y_hat||^2
-        and <q, x_hat> = <q V, y_hat> + <q, mu>: only the queries are rotated, the codes are
-        scanned as packed fields against the per-dimension level tables.  Returns device tensors
-        (dists f32 (nq, k), ids int32 (nq, k) holding uint32 ids): squared L2 distances ascending,
-        or inner products descending (the kernel's key negated plus f32(<q, mu>), one f32 add per
-        query)."""
-        Qy = self.rotate_queries(Q, metric)
-        st = self._state()
-        cd = codes if _arrays.is_tensor(codes) else torch.from_numpy(np.ascontiguousarray(codes, dtype=np.uint8))
-        cd = _arrays.to_device(cd, torch.uint8).contiguous()
-        mt = _native.METRIC_L2 if metric == "l2" else _native.METRIC_INNER_PRODUCT
-        d, i = _native.rankaware_flat_search(Qy, cd, st, int(k), mt, id_offset=int(id_offset))
-        if metric == "ip":
-            qmu = (self._queries(Q).to(torch.float64) @ st.mu).to(torch.float32)
-            d = -d + qmu[:, None]
-        return d, i
+    @classmethod
+    def from_state(cls, z) -> "RankAwareQuantizer":
+        q = cls(avg_bits=float(z["avg_bits"]), alpha=float(z["alpha"]), max_bits=int(z["max_bits"]),
+                seed=int(z["seed"]), packing=str(z["packing"]),
+                codebook=str(z["codebook"]) if "codebook" in z else "gaussian",
+                codebook_engine=str(z["codebook_engine"]) if "codebook_engine" in z else "saq")
+        q.mu, q.V, q.var = np.array(z["mu"]), np.array(z["V"]), np.array(z["var"])
+        q.bits = np.array(z["bits"], dtype=np.int64)
+        q.D = int(q.bits.shape[0])
+        ends = np.cumsum(2 ** q.bits)
+        cb = np.array(z["cb"], dtype=np.float64)
+        if cb.shape != (int(ends[-1]),) or q.V.shape != (q.D, q.D) or q.mu.shape != (q.D,):
+            raise ValueError("load(): inconsistent rank-aware quantizer state")
+        q.cb = [cb[e - 2 ** b:e] for e, b in zip(ends, q.bits)]
+        lv = np.array(z["levels"], dtype=np.float64)
+        q._levels = [lv[2 ** b - 1:2 ** (b + 1) - 1] for b in range(q.max_bits + 1)]
+        q._Dg = np.array(z["Dg"])
+        q._layout()
+        return q
 
     def get_compression_ratio(self, X) -> float:
         return float(int(X.shape[1]) * 4 / self.code_size)

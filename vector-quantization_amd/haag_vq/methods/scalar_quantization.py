@@ -20,6 +20,9 @@ from .base_quantizer import BaseQuantizer
 
 
 class ScalarQuantizer(BaseQuantizer):
+    qtype = "sq"
+    code_kind = "sq"
+
     def __init__(self, num_bits: int = 8):
         if num_bits not in [4, 8, 16]:
             raise ValueError(f"num_bits must be 4, 8, or 16, got {num_bits}")
@@ -104,6 +107,28 @@ class ScalarQuantizer(BaseQuantizer):
             rec = _native.sq_decode(ct[s:e].to(_arrays.device()).contiguous(), d, lo, den, self.num_bits)
             out[s:e] = _arrays.to_host(rec)
         return out
+
+    def flat_keys(self, codes_dev, Q_dev, k: int, mt: int, id_offset: int = 0):
+        """f32-fitted SQ: the codes are scanned as they are (an f64 fit decodes in f64 and rounds
+        to f32 afterwards, which the f32 dequantisation of the kernel does not reproduce)."""
+        if self.min is None or np.asarray(self.min).dtype != np.float32:
+            return super().flat_keys(codes_dev, Q_dev, k, mt, id_offset)
+        lo, den = self._params(torch.float32)
+        return _native.sq_flat_search(Q_dev, codes_dev.contiguous(), len(self.min), lo, den, self.num_bits, k, mt,
+                                      id_offset=id_offset)
+
+    def code_params(self) -> tuple:  # (lo, den)
+        return tuple(self._params(torch.float32))
+
+    def to_state(self) -> dict:
+        return dict(qtype=np.array(self.qtype), num_bits=np.array(self.num_bits), min=np.asarray(self.min),
+                    max=np.asarray(self.max))
+
+    @classmethod
+    def from_state(cls, z) -> "ScalarQuantizer":
+        q = cls(num_bits=int(z["num_bits"]))
+        q.min, q.max = np.array(z["min"]), np.array(z["max"])
+        return q
 
     def get_compression_ratio(self, X):
         original = X.shape[1] * 4

@@ -34,13 +34,8 @@ from ._ivf_shell import IvfShellIndex
 
 
 def _kind_of(q) -> Tuple[str, int]:
-    from ..lvq_quantization import LVQQuantizer
-    from ..scalar_quantization import ScalarQuantizer
-
-    if isinstance(q, ScalarQuantizer):
-        return "sq", int(q.num_bits)
-    if isinstance(q, LVQQuantizer):
-        return "lvq", int(q.num_bits)
+    if getattr(q, "code_kind", None) is not None:
+        return q.code_kind, int(q.num_bits)
     raise NotImplementedError(
         f"IvfQuantizedIndex is native for ScalarQuantizer (4 / 8 / 16 bits) and LVQQuantizer (1..8 bits); "
         f"the factory returned {type(q).__name__}")

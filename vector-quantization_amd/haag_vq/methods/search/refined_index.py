@@ -32,8 +32,6 @@ import torch
 from ... import _arrays, _native
 from ..base_quantizer import BaseQuantizer
 from ..base_search_index import BaseSearchIndex
-from ..lvq_quantization import LVQQuantizer
-from ..scalar_quantization import ScalarQuantizer
 from ._common import MAX_CANDIDATES  # noqa: F401  (what a base search returns at most; importable from here)
 from ._common import FLT_MAX, METRIC, candidate_count, check_metric, empty_results, results_to_host, save_npz
 
@@ -41,10 +39,8 @@ from ._common import FLT_MAX, METRIC, candidate_count, check_metric, empty_resul
 def _kind_of(refine: Optional[BaseQuantizer]) -> Tuple[str, int]:
     if refine is None:
         return "f32", 0
-    if isinstance(refine, ScalarQuantizer):
-        return "sq", int(refine.num_bits)
-    if isinstance(refine, LVQQuantizer):
-        return "lvq", int(refine.num_bits)
+    if getattr(refine, "code_kind", None) is not None:
+        return refine.code_kind, int(refine.num_bits)
     raise ValueError(f"RefinedIndex re-ranks on f32 rows (refine=None), ScalarQuantizer (4 / 8 / 16 bits) or "
                      f"LVQQuantizer (1..8 bits) codes, got {type(refine).__name__}")
 
@@ -90,10 +86,7 @@ class RefinedIndex(BaseSearchIndex):
         else:
             self._refine.fit(Xd)
             self._store = self._refine.compress(Xd)
-            if self._kind == "sq":
-                self._params = tuple(self._refine._params(torch.float32))
-            else:
-                self._params = (self._refine._mu_device(),)
+            self._params = self._refine.code_params()
         self._metric = metric
         self._N, self._D = int(Xd.shape[0]), int(Xd.shape[1])
 
