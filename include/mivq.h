@@ -369,14 +369,19 @@ int mivq_codebook1d_fit(const float* cols, int64_t n, int32_t d, const int32_t* 
  *   dist(q, i)   = ((lut[q][0][code_0] + lut[q][1][code_1]) + ...) + lut[q][M-1][code_M-1]
  * Results per query are the k smallest (dist, id) pairs in ascending (dist, id) order
  * (ties broken by the smaller global id = id_offset + row); missing slots (n < k) hold
- * dist = +inf, id = 0xFFFFFFFF. */
+ * dist = +inf, id = 0xFFFFFFFF.
+ * Any M up to 2^20 is searched (a larger M is MIVQ_ERR_UNSUPPORTED, and its size query 0): tables
+ * of up to 160 KiB per query (M * 2^nbits * 4 B) stay in LDS, larger ones are staged in chunks of
+ * subspaces, with the same sum in the same order.  The workspace holds per-part result lists
+ * only: nothing in it grows with n * nq or, past 160 KiB of tables, with M. */
 int mivq_adc_lut(const float* q, int64_t nq, int32_t d, int32_t M, int32_t nbits,
                  const float* centroids, int32_t metric, float* lut, void* stream);
 size_t mivq_adc_search_workspace_bytes(int64_t nq, int64_t n, int32_t M, int32_t nbits, int32_t k);
 /* codes: (n, M) one byte per sub-code (nbits <= 8; use mivq_pq_unpack for nbits < 8).
  * flags: MIVQ_ADC_AUTO (0) for every product call; the other bits are diagnostics / test
  * hooks and change no result except MIVQ_ADC_NO_RERUN (see below).  The workspace size does
- * not depend on flags. */
+ * not depend on flags.  Tables past 160 KiB per query have no filtered search: there every
+ * flag leaves the call as it is. */
 #define MIVQ_ADC_AUTO 0u          /* filtered search where the shape allows it, else the fp32 scan */
 #define MIVQ_ADC_FORCE_EXACT 1u   /* diagnostic: the fp32 scan for every query (same results)      */
 #define MIVQ_ADC_NO_RERUN 2u      /* test hook: queries the filter cannot certify are left NaN      */

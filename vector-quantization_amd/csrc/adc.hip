@@ -12,7 +12,8 @@
 //                      deterministic and identical for any row partition.
 // The tables come from adc_lut.hip, the per-wave lists go through topk.hip's merge, and
 // M = 16 / 32 searches of k <= 32 take adc_filtered.hip first: this scan then re-runs only the
-// queries that path could not certify.
+// queries that path could not certify.  Tables past one workgroup's LDS (adc_qb() == 0: more than
+// 160 KiB per query) go to adc_wide.hip's subspace-chunked scan, with the same sum and part lists.
 #include "adc_internal.h"
 #include "topk.h"
 
@@ -294,7 +295,8 @@ int64_t adc_fallback_chunks(int64_t nq, int64_t n, int k) {
 // The workspace of mivq_adc_search (nq, n > 0): the fp32 scan's part lists (parts, nq, k) --
 // distances at pd, ids at pi, sized for the scan of every query (nch_exact chunks) and, on a
 // filtered shape, for the re-run of the uncertified ones (nch_rerun) -- then the filtered
-// path's regions F.  QB == 0: the tables do not fit LDS, no search.
+// path's regions F.  QB == 0: the tables do not fit LDS, the wide scan's part lists (nch_exact
+// row ranges) and nothing else; total == 0 where M is past that scan's bound: no search.
 struct AdcSearchLayout {
     int QB;
     bool fshape;
@@ -306,7 +308,14 @@ struct AdcSearchLayout {
 AdcSearchLayout adc_search_layout(int64_t nq, int64_t n, int M, int nbits, int k) {
     AdcSearchLayout L{};
     L.QB = adc_qb(M, 1 << nbits);
-    if (L.QB == 0) return L;
+    if (L.QB == 0) {
+        if (M > kAdcWideMaxM) return L;
+        L.nch_exact = adc_wide_chunks(nq, n);
+        L.parts = L.nch_exact * kScanWaves;
+        L.pi = align_up((size_t)L.parts * nq * k * 4, 256);
+        L.total = 2 * L.pi;
+        return L;
+    }
     L.fshape = adc_filtered_shape(M, 1 << nbits, k);
     L.nch_exact = adc_chunks(nq, n, L.QB);
     L.nch_rerun = L.fshape ? adc_fallback_chunks(nq, n, k) : 0;
@@ -363,7 +372,8 @@ extern "C" int mivq_adc_search(const float* lut, int64_t nq, const uint8_t* code
     MIVQ_REQUIRE(nbits >= 1 && nbits <= 8, MIVQ_ERR_UNSUPPORTED, "adc_search: nbits=%d", nbits);
     MIVQ_REQUIRE(k <= 256, MIVQ_ERR_UNSUPPORTED, "adc_search: k=%d > 256", k);
     const int ksub = 1 << nbits;
-    MIVQ_REQUIRE(adc_qb(M, ksub) > 0, MIVQ_ERR_UNSUPPORTED, "adc_search: M*ksub=%d tables do not fit LDS", M * ksub);
+    const bool wide = adc_qb(M, ksub) == 0;  // tables past one workgroup's LDS: adc_wide.hip
+    MIVQ_REQUIRE(!wide || M <= kAdcWideMaxM, MIVQ_ERR_UNSUPPORTED, "adc_search: M=%d > %d", M, kAdcWideMaxM);
     MIVQ_REQUIRE(id_offset >= 0 && id_offset + n <= (int64_t)kNoId, MIVQ_ERR_INVALID,
                  "adc_search: global ids must fit uint32");
     if (nq == 0) return MIVQ_OK;
@@ -382,6 +392,13 @@ extern "C" int mivq_adc_search(const float* lut, int64_t nq, const uint8_t* code
     unsigned char* ws = static_cast<unsigned char*>(workspace);
     float* pd = reinterpret_cast<float*>(ws + L.pd);
     uint32_t* pi = reinterpret_cast<uint32_t*>(ws + L.pi);
+    if (wide) {  // no filtered variant: the flags change nothing
+        hipError_t e = launch_adc_wide(lut, nq, codes, n, M, nbits, k, id_offset, pd, pi, st);
+        if (e != hipSuccess) return set_error(MIVQ_ERR_HIP, "adc_wide_scan: %s", hipGetErrorString(e));
+        e = launch_topk_merge(pd, pi, (int)L.parts, nq, k, dists, ids, st);
+        if (e != hipSuccess) return set_error(MIVQ_ERR_HIP, "topk_merge: %s", hipGetErrorString(e));
+        return MIVQ_OK;
+    }
     // the filtered path (integer-LUT scan + exact re-rank + certificate; the fp32 scan re-runs
     // only the uncertified queries): same results, ~half the LDS traffic per (query, row)
     const bool filtered = L.fshape && reinterpret_cast<uintptr_t>(codes) % 16 == 0 &&

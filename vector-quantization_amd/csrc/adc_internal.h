@@ -1,4 +1,4 @@
-// adc_internal.h — what adc.hip, adc_filtered.hip and exact_search.hip share; the query-block
+// adc_internal.h — what adc.hip, adc_filtered.hip, adc_wide.hip and exact_search.hip share; the query-block
 // dispatch serves the searches over probed lists too (ivf_code.hip, ivf_listpq.hip).
 #pragma once
 
@@ -46,5 +46,14 @@ bool adc_filtered_offsets_fit(const AdcFilteredLayout& L, int64_t n, int M);
 hipError_t launch_filtered(int M, const float* lut, int64_t nq, const uint8_t* codes, int64_t n, int k,
                            int64_t id_offset, unsigned char* ws, const AdcFilteredLayout& L, float* dists,
                            uint32_t* ids, hipStream_t st);
+
+// ---------------------------------------------------------------- wide scan (adc_wide.hip)
+// The scan of the shapes whose tables do not fit LDS.  Row ranges per query block; every range
+// yields kScanWaves part lists.
+constexpr int kAdcWideMaxM = 1 << 20;
+int64_t adc_wide_chunks(int64_t nq, int64_t n);
+// Part lists (adc_wide_chunks * kScanWaves, nq, k) into (pd, pi).
+hipError_t launch_adc_wide(const float* lut, int64_t nq, const uint8_t* codes, int64_t n, int M, int nbits, int k,
+                           int64_t id_offset, float* pd, uint32_t* pi, hipStream_t st);
 
 }  // namespace mivq

@@ -178,8 +178,16 @@ class ProductQuantizer(BaseQuantizer):
         search up to fp32 rounding on near-ties, without materialising x_hat."""
         cd = codes_dev.to(torch.uint8).contiguous()
         u8 = cd if self.B == 8 else _native.pq_unpack(cd, self.M, self.B)
-        lut = _native.adc_lut(Q_dev, self.centroids_device, self.B, mt)
-        return _native.adc_search(lut, u8, k, self.B, id_offset=id_offset)
+        # the LUT is nq x M x 2^B floats (786 MB per 1000 queries at M = 768): query blocks keep one
+        # LUT within 1 GiB; results are per query, so the blocks concatenate
+        qb = max(1, (1 << 30) // (self.M * (1 << self.B) * 4))
+        outs = []
+        for s in range(0, max(int(Q_dev.shape[0]), 1), qb):
+            lut = _native.adc_lut(Q_dev[s:s + qb], self.centroids_device, self.B, mt)
+            outs.append(_native.adc_search(lut, u8, k, self.B, id_offset=id_offset))
+        if len(outs) == 1:
+            return outs[0]
+        return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
 
     def to_state(self) -> dict:
         return dict(qtype=np.array(self.qtype), M=np.array(self.M), B=np.array(self.B), centroids=_arrays.to_host(self._C))
