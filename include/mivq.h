@@ -231,6 +231,29 @@ int mivq_extrabitq_finish(const double* y, int64_t n, int32_t d, const uint8_t* 
 /* s = o . P (transpose 0) or o . P^T (transpose 1); o, s: (n, d) f64 row-major, P: (d, d). */
 int mivq_extrabitq_rotate(const double* o, int64_t n, int32_t d, const double* P, int32_t transpose,
                           double* s, void* stream);
+/* The fast Hadamard rotation: an orthogonal map of O(D log D) per row with rounds * D bits of
+ * state, in place of the dense P.  signs: (rounds, d) u8 of 0 / 1 on the device, 1 negates.
+ * T = the largest power of two <= d, h = d / 2 (integer).  For a row x, for r = 0 .. rounds-1:
+ *   1. x[i] = -x[i] wherever signs[r, i] == 1
+ *   2. x[off : off+T] = H_T . x[off : off+T] / sqrt(T), off = 0 for even r and d - T for odd r,
+ *      H_T the Sylvester Hadamard matrix, H[i, j] = (-1)^popcount(i & j)
+ *   3. only if T < d: for i in [0, h), j = i + d - h:
+ *      (x[i], x[j]) = ((x[i] + x[j]) / sqrt(2), (x[i] - x[j]) / sqrt(2))   (odd d: the middle stays)
+ * Every step is orthogonal and its own inverse; inverse != 0 runs the steps of each round
+ * backwards and the rounds in reverse order.  All arithmetic is fp64.  in, out: (n, d) f64,
+ * in == out is allowed.  rounds in 1..8 and d <= 16384, MIVQ_ERR_UNSUPPORTED otherwise. */
+int mivq_fht_rotate(const double* in, int64_t n, int32_t d, const uint8_t* signs, int32_t rounds,
+                    int32_t inverse, double* out, void* stream);
+/* Extended RaBitQ with that rotation, one pass per row and no workspace.  encode_fht reads x
+ * (f32 or f64) once and writes the code row once: the bits of mivq_extrabitq_normalize ->
+ * mivq_fht_rotate -> mivq_extrabitq_quantize.  decode_fht: the bits of mivq_extrabitq_dequantize
+ * -> mivq_fht_rotate (inverse) -> mivq_extrabitq_finish. */
+int mivq_extrabitq_encode_fht(const void* x, int32_t x_is_f64, int64_t n, int32_t d,
+                              const double* centroid, const uint8_t* signs, int32_t rounds,
+                              const double* levels, int32_t nbits, uint8_t* codes, void* stream);
+int mivq_extrabitq_decode_fht(const uint8_t* codes, int64_t n, int32_t d, const double* centroid,
+                              const uint8_t* signs, int32_t rounds, const double* levels,
+                              int32_t nbits, float* out, void* stream);
 /* Exact top-k over Extended RaBitQ codes, undecoded, in the rotated domain.  P is orthogonal and
  * x_hat = (o_hat . P^T) nrm + c, so ||q - x_hat||^2 = ||(q - c) P - y_hat||^2 and
  * <q, x_hat> = <q P, y_hat> + <q, c> with y_hat = o_hat nrm: the caller rotates the queries

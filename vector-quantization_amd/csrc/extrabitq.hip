@@ -11,18 +11,13 @@
 //           x_hat = f32((o_hat . P^T) * nrm + c)                             [finish]
 // The two D x D rotations (o . P, o_hat . P^T; extended_rabitq.py:140,196) run on the library's
 // fp64 MFMA GEMM, mivq_extrabitq_rotate in gemm_f64.hip; this file holds the per-row steps.
-// One wavefront per row for the reductions (tree order: the factors match numpy to ~1e-15
+// The per-row bodies are the device functions of extrabitq_rows.h, shared with the fused
+// Hadamard-rotation kernels of fht.hip.  One wavefront per row for the reductions (tree order: the factors match numpy to ~1e-15
 // relative, the indices are exact except where s lies within rounding of a level midpoint).
-#include "mivq_common.h"
+#include "extrabitq_rows.h"
 
 namespace mivq {
 namespace {
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void erq_normalize_kernel(const T* __restrict__ x, int64_t n, int d,
@@ -31,16 +26,8 @@ __global__ __launch_bounds__(256) void erq_normalize_kernel(const T* __restrict_
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n) return;
-    double ss = 0.0;
-    for (int j = lane; j < d; j += 64) {
-        const double r = __dsub_rn((double)x[row * d + j], c[j]);
-        o[row * d + j] = r;
-        ss = __fma_rn(r, r, ss);
-    }
-    ss = wave_sum_d(ss);
-    const double nr = sqrt(ss);
-    const double inv = fmax(nr, 1e-12);
-    for (int j = lane; j < d; j += 64) o[row * d + j] = __ddiv_rn(o[row * d + j], inv);
+    MemRow r{o + row * d, lane};
+    const double nr = erq_normalize_row(x + row * d, d, (d + 63) / 64, c, lane, r);
     if (lane == 0) nrm[row] = nr;
 }
 
@@ -51,85 +38,25 @@ __global__ __launch_bounds__(256) void erq_quantize_kernel(const double* __restr
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n) return;
-    const int L = 1 << nbits;
-    const int ib = (d * nbits + 7) / 8;
-    const int cs = ib + 8;
-    uint8_t* code = codes + row * cs;
-    const double sq = sqrt((double)d);
-    double num = 0.0, den = 0.0;
-    // lane owns groups of 8 dims: 8 B-bit indices are exactly nbits whole bytes of the
-    // MSB-first stream (np.packbits order), bits past d*nbits stay 0
-    const int groups = (d + 7) / 8;
-    for (int g = lane; g < groups; g += 64) {
-        uint64_t bits = 0;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int j = g * 8 + u;
-            int idx = 0;
-            if (j < d) {
-                const double s = __dmul_rn(s_raw[row * d + j], sq);
-                for (int q = 0; q + 1 < L; ++q) {
-                    const double mid = __dmul_rn(0.5, __dadd_rn(levels[q], levels[q + 1]));
-                    idx += (mid < s) ? 1 : 0;  // searchsorted(side="left")
-                }
-                const double sh = levels[idx];
-                num = __fma_rn(s, sh, num);
-                den = __fma_rn(sh, sh, den);
-            }
-            bits = (bits << nbits) | (uint64_t)idx;
-        }
-        for (int b = 0; b < nbits; ++b) {
-            const int byte = g * nbits + b;
-            if (byte < ib) code[byte] = (uint8_t)(bits >> (8 * (nbits - 1 - b)));
-        }
-    }
-    num = wave_sum_d(num);
-    den = wave_sum_d(den);
-    if (lane == 0) {
-        const double t = den > 1e-12 ? __ddiv_rn(num, den) : 1.0;
-        const float nf = (float)nrm[row], tf = (float)t;
-        const uint32_t u0 = __float_as_uint(nf), u1 = __float_as_uint(tf);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            code[ib + q] = (uint8_t)(u0 >> (8 * q));
-            code[ib + 4 + q] = (uint8_t)(u1 >> (8 * q));
-        }
-    }
+    const int cs = (d * nbits + 7) / 8 + 8;
+    erq_quantize_row(s_raw + row * d, d, levels, nbits, nrm[row], codes + row * cs, lane);
 }
 
 __global__ void erq_dequantize_kernel(const uint8_t* __restrict__ codes, int64_t n, int d,
                                       const double* __restrict__ levels, int nbits, double* __restrict__ o_hat) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n * (int64_t)d) return;
-    const int64_t i = e / d;
-    const int j = (int)(e % d);
     const int ib = (d * nbits + 7) / 8;
-    const uint8_t* code = codes + i * (ib + 8);
-    int idx = 0;
-    for (int u = 0; u < nbits; ++u) {
-        const int gb = j * nbits + u;
-        idx = (idx << 1) | ((code[gb >> 3] >> (7 - (gb & 7))) & 1);
-    }
-    uint32_t tu = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) tu |= (uint32_t)code[ib + 4 + q] << (8 * q);
-    const double t = (double)__uint_as_float(tu);
-    o_hat[e] = __dmul_rn(__ddiv_rn(levels[idx], sqrt((double)d)), t);
+    const uint8_t* code = codes + (e / d) * (ib + 8);
+    o_hat[e] = erq_dequantize_elem(code, (int)(e % d), d, levels, nbits, erq_trailer(code, ib + 4));
 }
 
 __global__ void erq_finish_kernel(const double* __restrict__ y, int64_t n, int d, const uint8_t* __restrict__ codes,
                                   int nbits, const double* __restrict__ c, float* __restrict__ out) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n * (int64_t)d) return;
-    const int64_t i = e / d;
-    const int j = (int)(e % d);
     const int ib = (d * nbits + 7) / 8;
-    const uint8_t* code = codes + i * (ib + 8);
-    uint32_t nu = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) nu |= (uint32_t)code[ib + q] << (8 * q);
-    const double nr = (double)__uint_as_float(nu);
-    out[e] = (float)__dadd_rn(__dmul_rn(y[e], nr), c[j]);
+    out[e] = erq_finish_elem(y[e], erq_trailer(codes + (e / d) * (ib + 8), ib), c[e % d]);
 }
 
 }  // namespace

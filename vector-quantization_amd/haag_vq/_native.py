@@ -81,6 +81,9 @@ SIGNATURES = {
     "mivq_extrabitq_dequantize": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp]),
     "mivq_extrabitq_finish": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp]),
     "mivq_extrabitq_rotate": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp]),
+    "mivq_fht_rotate": (_c.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "mivq_extrabitq_encode_fht": (_c.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp]),
+    "mivq_extrabitq_decode_fht": (_c.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp]),
     "mivq_rankaware_center": (_c.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "mivq_rankaware_quantize": (_c.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "mivq_rankaware_dequantize": (_c.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
@@ -765,6 +768,71 @@ def extrabitq_decode(codes: torch.Tensor, c: torch.Tensor, P: torch.Tensor, leve
     _check(P, "P", torch.float64, 2)
     y = gemm_f64(extrabitq_dequantize(codes, levels, nbits, P.shape[0]), P, True)
     return extrabitq_finish(y, codes, c, nbits)
+
+
+FHT_ROUNDS = 4  # rounds of the fast Hadamard rotation every fitted state uses (include/mivq.h)
+
+
+def _fht_signs_check(signs: torch.Tensor, d: int) -> int:
+    _check(signs, "signs", torch.uint8, 2)
+    if signs.shape[1] != d:
+        raise ValueError(f"fht: signs are (rounds, {signs.shape[1]}), rows have d={d}")
+    return int(signs.shape[0])
+
+
+def fht_rotate(x: torch.Tensor, signs: torch.Tensor, inverse: bool = False,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The fast Hadamard rotation of (n, d) f64 rows (mivq_fht_rotate; the rule is in include/mivq.h):
+    signs (rounds, d) u8 of 0 / 1, `inverse` undoes it, `out` may be x itself."""
+    _check(x, "x", torch.float64, 2)
+    n, d = x.shape
+    rounds = _fht_signs_check(signs, d)
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _check(out, "out", torch.float64, 2)
+        if out.shape != x.shape:
+            raise ValueError(f"out shape {tuple(out.shape)} != {tuple(x.shape)}")
+    _call("mivq_fht_rotate", _ptr(x), n, d, _ptr(signs), rounds, 1 if inverse else 0, _ptr(out), _stream())
+    return out
+
+
+def extrabitq_encode_fht(x: torch.Tensor, c: torch.Tensor, signs: torch.Tensor, levels: torch.Tensor,
+                         nbits: int) -> torch.Tensor:
+    """Codes of ExtendedRaBitQuantizer(rotation="fht").compress in one pass over x (f32 or f64):
+    the bits of extrabitq_normalize -> fht_rotate -> extrabitq_quantize."""
+    _extrabitq_bits_check(nbits)
+    if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"extrabitq: unsupported dtype {getattr(x, 'dtype', type(x))}")
+    _check(x, "x", x.dtype, 2)
+    _check(c, "c", torch.float64, 1)
+    _check(levels, "levels", torch.float64, 1)
+    n, d = x.shape
+    rounds = _fht_signs_check(signs, d)
+    if c.numel() != d or levels.numel() != 1 << nbits:
+        raise ValueError(f"extrabitq: c of {c.numel()} / {levels.numel()} levels for d={d}, {nbits} bits")
+    out = torch.empty((n, extrabitq_code_size(d, nbits)), dtype=torch.uint8, device=x.device)
+    _call("mivq_extrabitq_encode_fht", _ptr(x), 1 if x.dtype == torch.float64 else 0, n, d, _ptr(c), _ptr(signs),
+          rounds, _ptr(levels), nbits, _ptr(out), _stream())
+    return out
+
+
+def extrabitq_decode_fht(codes: torch.Tensor, c: torch.Tensor, signs: torch.Tensor, levels: torch.Tensor,
+                         nbits: int) -> torch.Tensor:
+    """(n, d) f32 of ExtendedRaBitQuantizer(rotation="fht").decompress in one pass: the bits of
+    extrabitq_dequantize -> fht_rotate(inverse) -> extrabitq_finish."""
+    _check(c, "c", torch.float64, 1)
+    _check(levels, "levels", torch.float64, 1)
+    d = c.numel()
+    _extrabitq_code_check(codes, d, nbits, "extrabitq_decode_fht")
+    rounds = _fht_signs_check(signs, d)
+    if levels.numel() != 1 << nbits:
+        raise ValueError(f"extrabitq: levels has {levels.numel()} entries, expected {1 << nbits}")
+    n = codes.shape[0]
+    out = torch.empty((n, d), dtype=torch.float32, device=codes.device)
+    _call("mivq_extrabitq_decode_fht", _ptr(codes), n, d, _ptr(c), _ptr(signs), rounds, _ptr(levels), nbits, _ptr(out),
+          _stream())
+    return out
 
 
 def extrabitq_flat_search(qy: torch.Tensor, codes: torch.Tensor, levels: torch.Tensor, nbits: int, k: int,

@@ -3,7 +3,8 @@
 <q, x_hat> = <q R, y_hat> + <q, centre>.  Only the queries are rotated; no row is decoded.
 
 A quantizer supplies ``D``, ``_fitted()``, a ``_state()`` that begins with (centre (D,), R (D, D))
-in fp64 on the device, and ``_scan(Qy, codes, k, mt, id_offset)``: its ``mivq_*_flat_search`` of
+in fp64 on the device (a quantizer whose R is no matrix overrides ``_rotate`` and may put
+anything second), and ``_scan(Qy, codes, k, mt, id_offset)``: its ``mivq_*_flat_search`` of
 rotated queries over packed codes (kernel keys ascending, IP negated and without <q, centre>).
 """
 
@@ -32,9 +33,12 @@ class RotatedSearch:
         if metric not in ("l2", "ip"):
             raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
         Qd = self._queries(Q)
-        c, R = self._state()[:2]
-        return _native.gemm_f64(_native.rankaware_center(Qd, c if metric == "l2" else torch.zeros_like(c)), R,
-                                False).to(torch.float32)
+        c = self._state()[0]
+        return self._rotate(_native.rankaware_center(Qd, c if metric == "l2" else torch.zeros_like(c))).to(torch.float32)
+
+    def _rotate(self, Xc: torch.Tensor) -> torch.Tensor:
+        """``Xc R`` for centred fp64 rows on the device."""
+        return _native.gemm_f64(Xc, self._state()[1], False)
 
     def search_codes(self, codes, Q, k: int, metric: str = "l2", id_offset: int = 0):
         """Top-k of Q over ``codes`` without decoding them (``_scan``, k <= 256).  Returns device
